@@ -93,6 +93,9 @@ def parse():
                     help="skip the live rocprofv3 --pmc passes (roofline.traffic / mfma_util then carry the stored profile values)")
     ap.add_argument("--no-reference-order", action="store_true",
                     help="skip the bounded drop-in-route entry (\"reference_order\") of the default N = 1 int4 line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its greedy tokens and logits) as "
+                         "DIR/<name>.npy, float64 / float32, <= 64 MB in all (rank 0)")
     return ap.parse_args()
 
 
@@ -882,6 +885,28 @@ def choose_allreduce(ps, elems, dev, strict):
     return label, reason
 
 
+DUMP_BUDGET = 64 << 20  # bytes, all --dump-outputs files together
+
+
+def dump_outputs(dirpath, tokens, logits):
+    """``--dump-outputs``: the last timed step's results as .npy files -- ``tokens`` [B] (greedy ids, float64: exact) and
+    ``logits`` [B, V] (float32).  Logits past the budget are cut to a fixed seeded sample of rows, named in ``logits_rows``."""
+    import numpy as np
+
+    os.makedirs(dirpath, exist_ok=True)
+    out = {"tokens": tokens.detach().cpu().numpy().astype(np.float64)}
+    lg = logits.detach().float().cpu()
+    room = (DUMP_BUDGET - out["tokens"].nbytes) // (lg.shape[1] * 4 + 8)
+    if lg.shape[0] > room:
+        rows = torch.randperm(lg.shape[0], generator=torch.Generator().manual_seed(0))[:room].sort().values
+        lg = lg[rows]
+        out["logits_rows"] = rows.numpy().astype(np.float64)
+    out["logits"] = lg.numpy()
+    for name, arr in out.items():
+        np.save(os.path.join(dirpath, name + ".npy"), arr)
+    return sorted(out)
+
+
 def self_launch(args) -> int:
     """``python bench.py --gpus N`` without a launcher: start the N ranks ourselves (the reference's TP entry point spawns
     its workers itself too, lite_llama/cli.py:37-112, 397-476) -- one process per GPU under torch.distributed.run on a free
@@ -1033,6 +1058,18 @@ def main():
         print("[bench] gloo collectives cannot be captured: measuring eager launches", file=sys.stderr, flush=True)
     graph_note = "hipGraph" if use_graph else "eager (--no-graph or uncapturable backend)"
     graph_error = None
+    last_logits = []
+    if args.dump_outputs:
+        # keep a handle on the logits of the most recent forward: a captured step's output buffer is refilled by every replay
+        # (the last capture is the graph that replays last), an eager step's is the step's own; the launches are unchanged
+        forward = model.forward
+
+        def keep_logits(*a, **k):
+            out = forward(*a, **k)
+            last_logits[:] = [out]
+            return out
+
+        model.forward = keep_logits
     try:
         if args.steps_per_graph > 1 and (args.warmup % args.steps_per_graph or args.steps % args.steps_per_graph):
             raise SystemExit("--steps-per-graph must divide --warmup and --steps (the timed region starts on a replay boundary)")
@@ -1065,6 +1102,11 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
     assert out.shape == (args.batch, total)
+    dumped = None
+    if args.dump_outputs:
+        del model.forward
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, out[:, -1], last_logits[0][:, -1, :])
 
     global_batch = args.batch * dp
     tokens = global_batch * args.steps
@@ -1097,6 +1139,8 @@ def main():
                           "achieved_GBps_per_gpu": round(step_bytes / (elapsed / args.steps) / 1e9, 1),
                           "frac_of_8TBps": round(step_bytes / (elapsed / args.steps) / PEAK_HBM, 4)},
     }
+    if dumped:
+        result["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
     w_lin_alg, w_head_alg, _ = algorithmic_bytes(geo, args.quant, args.batch, 0, tp)
     result["memory"] = {
         "weights_resident_bytes": int(model.weight_bytes()),   # every distinct parameter / load-time-layout storage of this rank

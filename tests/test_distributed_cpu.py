@@ -54,9 +54,17 @@ def _free_port():
     return port
 
 
+def _host_only():
+    """A rank of these tests is a host process on any box: gloo collectives on CPU tensors, and no GPU runtime opened (on a
+    GPU box the backend would default to RCCL, and eight ranks would all open the one device)."""
+    os.environ["LL_DIST_BACKEND"] = "gloo"
+    torch.cuda.is_available = lambda: False
+
+
 def _worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    _host_only()
     try:
         ps.init_tensor_parallel(rank, world, master_port=port)
         from lite_llama_amd.linear import ColumnParallelLinear, RowParallelLinear
@@ -147,6 +155,7 @@ def _plan_worker(rank, world, port, q):
     all-reduce.  The parent compares with the same arithmetic on the unsharded matrices."""
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
+    _host_only()
     try:
         ps.init_tensor_parallel(rank, world, master_port=port)
         out = _block_math(*_plan_case())
