@@ -137,6 +137,54 @@ static inline bool ll_aligned16(const void* p) { return (reinterpret_cast<uintpt
 
 #define LL_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? LL_OK : LL_ERR_LAUNCH)
 
+// The current device's index, or -1 when there is none (host-side plan queries without a GPU) or it is past the caches below.
+inline int ll_device_slot() {
+  int dev = -1;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16 ? dev : -1;
+}
+
+// Properties of the current device, queried once per device.  Without one: gfx950's 256 CUs and no LDS limit (plans assume
+// the MI355X).
+struct LLDeviceProps {
+  int cus = 256;
+  int lds_optin = 1 << 30;  // bytes of dynamic LDS a workgroup may opt into
+};
+inline const LLDeviceProps& ll_device_props() {
+  static LLDeviceProps props[16];
+  static bool queried[16] = {false};
+  static const LLDeviceProps none;
+  const int dev = ll_device_slot();
+  if (dev < 0) return none;
+  if (!queried[dev]) {
+    hipDeviceProp_t prop;
+    int v = 0;
+    if (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) props[dev].cus = prop.multiProcessorCount;
+    props[dev].lds_optin =
+        hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess && v > 0 ? v : 160 * 1024;
+    queried[dev] = true;
+  }
+  return props[dev];
+}
+inline int ll_num_cus() { return ll_device_props().cus; }
+
+// Lets Kernel launch with `bytes` (> 64 KB) of dynamic LDS: set once per (kernel instantiation, device).
+template <auto Kernel>
+inline void ll_lds_opt_in(int bytes) {
+  static bool done[16] = {false};
+  const int dev = ll_device_slot();
+  if (dev < 0 || done[dev]) return;
+  (void)hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  done[dev] = true;
+}
+
+// ceil(2^32 / d): umulhi(x, ll_magic_u32(d)) == x / d for x * d < 2^32.  0 for d <= 1 (callers special-case d == 1) and for
+// d >= 2^31.
+static inline uint32_t ll_magic_u32(int64_t d) {
+  return d <= 1 || d >= (1ll << 31) ? 0u : (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d);
+}
+
+__device__ __forceinline__ void ll_s_barrier() { asm volatile("s_barrier" ::: "memory"); }
+
 // Reductions over the four 16-lane rows of a wave (lanes t, t + 16, t + 32, t + 48) with the gfx950 row-swap VALU
 // instructions instead of two ds_bpermute round trips through the LDS pipe: v_permlane16_swap exchanges the odd rows of
 // its first operand with the even rows of its second, v_permlane32_swap the upper half of the first with the lower half

@@ -956,15 +956,15 @@ extern "C" int ll_flash_decoding_num_partitions(int64_t max_len) {
 // Waves of the one-workgroup-per-(row, KV head group) decode form for contexts of up to max_len tokens, launched as `workgroups`
 // = batch x KV heads x head groups workgroups; 0: the form does not apply.  Up to FD_GROUP_MAX partitions: a wave per partition
 // (whatever the batch: round 2's measurement).  More (round 6): FD_GROUP_MAX waves that walk the partitions -- taken when the
-// launch alone fills half the chip (128 workgroups); smaller batches keep a workgroup per partition + the counter merge, which
-// spreads ONE row's context over many CUs.
+// launch alone fills half the chip (a workgroup per two CUs: 128 on the MI355X); smaller batches keep a workgroup per partition +
+// the counter merge, which spreads ONE row's context over many CUs.
 #define FD_LOOP_MAX 256  // partitions (32 768 tokens)
 extern "C" int ll_flash_decoding_group_waves(int64_t max_len, int64_t workgroups) {
   static const bool no_loop = getenv("LL_FD_NO_LOOP") != nullptr;  // A/B knob, read once
   const int64_t np = (max_len + FD_PART - 1) / FD_PART;
   if (np < 2) return 0;
   if (np <= FD_GROUP_MAX) return (int)np;
-  return (!no_loop && np <= FD_LOOP_MAX && workgroups >= 128) ? FD_GROUP_MAX : 0;
+  return (!no_loop && np <= FD_LOOP_MAX && 2 * workgroups >= ll_num_cus()) ? FD_GROUP_MAX : 0;
 }
 
 template <int DT>
@@ -998,14 +998,8 @@ static int launch_fd(void* out, const void* q, const void* kc, const void* vc, c
 #define LL_FD1XK(DD, FU, RO, GG, GR, K8, QN, QI)                                                            \
   {                                                                                                  \
     constexpr int tile_bytes_ = 32 * (DD + 8) * 2;                                                   \
-    if (GR) {                                                                                        \
-      static bool attr_ = false;                                                                     \
-      if (!attr_) {                                                                                  \
-        (void)hipFuncSetAttribute((const void*)fd_stage1<DT, DD, FU, RO, GG, GR, K8, QN, QI>,             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, FD_GROUP_MAX * tile_bytes_ + 18 * DD * 2); \
-        attr_ = true;                                                                                \
-      }                                                                                              \
-    }                                                                                                \
+    if (GR)                                                                                          \
+      ll_lds_opt_in<fd_stage1<DT, DD, FU, RO, GG, GR, K8, QN, QI>>(FD_GROUP_MAX * tile_bytes_ + 18 * DD * 2); \
     fd_stage1<DT, DD, FU, RO, GG, GR, K8, QN, QI><<<(GR) ? dim3(1, grid.y, grid.z) : grid, (GR) ? 64 * gw : 64, \
                                         ((GR) ? gw : 1) * tile_bytes_ + ((GR) ? 18 * DD * 2 : 0), st>>>( \
         (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, table, req, seq, mid_o, mid_lse, hq, hkv, nparts, \

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "gemm_debug.h"  // SS_TL / SS_TLC: in-kernel stamps of -DSS_TIMELINE builds (empty in the product build)
+#include "gemm_engines.h"
 #include "gemm_w4_common.h"
 
 #define SS_CONSUMERS 8
@@ -54,23 +55,6 @@ struct SSParams {
                 int p_kb_rem, int p_RB, uint32_t p_rb_magic, int p_total, int p_cap, int p_m, const uint16_t* __restrict__ p_x, \
                 float* __restrict__ p_out, int p_x_stride, unsigned long long* p_tl
 #define SS_PASS(P) P.wp, P.sp, P.n, P.chunks, P.gshift, P.kb_base, P.kb_rem, P.RB, P.rb_magic, P.total, P.cap, P.m, P.x, P.out, P.x_stride, P.tl
-
-
-__device__ __forceinline__ void ss_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-// at most `n` of this wave's memory operations may still be in flight (n <= 16)
-__device__ __forceinline__ void ss_wait_outstanding(int n) {
-  switch (n) {
-    case 0: v3_vmcnt<0>(); break;
-    case 2: v3_vmcnt<2>(); break;
-    case 4: v3_vmcnt<4>(); break;
-    case 6: v3_vmcnt<6>(); break;
-    case 8: v3_vmcnt<8>(); break;
-    case 12: v3_vmcnt<12>(); break;
-    case 16: v3_vmcnt<16>(); break;
-    default: v3_vmcnt<0>(); break;
-  }
-}
 
 // MT: 32-row batch halves (1: M <= 32, 2: M <= 64); R: row groups per work item (8 / R k-quarters per row group);
 // P: pieces (1 KB of packed weights = 32 rows x 64 k) per consumer wave at most; NKB > 0: every k-slice is exactly NKB 64-k blocks
@@ -128,12 +112,12 @@ __global__ __launch_bounds__(SS_THREADS) void wss_kernel(SS_ARGS) {
     }
     SS_TL(1)
     if constexpr (EXACT) v3_vmcnt<((SNC - SNC0) * PPL <= 63 ? (SNC - SNC0) * PPL : 0)>();
-    else ss_wait_outstanding((nC - nC0) * PPL);
+    else ll_wait_outstanding((nC - nC0) * PPL);
     SS_TL(2)
-    ss_barrier();  // A: chunks [0, nC0) of the slice are in LDS
+    ll_s_barrier();  // A: chunks [0, nC0) of the slice are in LDS
     v3_vmcnt<0>();
     SS_TL(3)
-    ss_barrier();  // B: all of it
+    ll_s_barrier();  // B: all of it
     return;
   }
 
@@ -201,11 +185,11 @@ __global__ __launch_bounds__(SS_THREADS) void wss_kernel(SS_ARGS) {
     SS_TL_PIECE_DONE(i, acc[MT - 1][15])
   };
   f16x8 a0[4][MT], a1[4][MT];
-  ss_barrier();  // A
+  ll_s_barrier();  // A
   SS_TL(2)
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
-    if (st == 1) ss_barrier();  // B
+    if (st == 1) ll_s_barrier();  // B
     read_x(a0, st * PH);
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
@@ -281,17 +265,6 @@ static const SSKnobs& ss_knobs() {
   return k;
 }
 
-static int ss_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // the slice geometry of (kbs k-blocks, S slices): most activation chunks any slice touches
 static int ss_max_chunks(int kbs, int S) {
   const int base = kbs / S, rem = kbs % S;
@@ -311,7 +284,7 @@ static SSPlan ss_plan(int64_t m, int64_t n, int64_t k, int group_size) {
   SSPlan best;
   const SSKnobs& kn = ss_knobs();
   if (!kn.on || !ll_w4a16_prepacked_supported(m, n, k, group_size)) return best;
-  const int cus = ss_num_cus();
+  const int cus = ll_num_cus();
   const int rgs = (int)(n / 32), kbs = (int)(k / 64);
   const int mt = m > 32 ? 2 : 1;
   double best_cost = 1e30;
@@ -351,7 +324,7 @@ static SSPlan ss_plan(int64_t m, int64_t n, int64_t k, int group_size) {
   return best;
 }
 
-// planes the short-stream engine leaves for (m, n, k); 0: the launch is not its (gemm_w4_v3.hip asks)
+// planes the short-stream engine leaves for (m, n, k); 0: the launch is not its (gemm_w4_dispatch.hip asks)
 int ss_partials_slices(int64_t m, int64_t n, int64_t k, int group_size) {
   const SSPlan pl = ss_plan(m, n, k, group_size);
   return pl.ok ? pl.S : 0;
@@ -369,17 +342,11 @@ extern "C" int ll_w4a16_short_plan(int64_t m, int64_t n, int64_t k, int group_si
 
 template <int MT, int R, int P, int NKB>
 static void ss_go(const SSParams& p, const SSPlan& pl, hipStream_t st) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)wss_kernel<MT, R, P, NKB>, hipFuncAttributeMaxDynamicSharedMemorySize, SS_MAX_CHUNKS * 2 * 32 * 256);
-    attr_set[dev] = true;
-  }
+  ll_lds_opt_in<wss_kernel<MT, R, P, NKB>>(SS_MAX_CHUNKS * 2 * 32 * 256);
   wss_kernel<MT, R, P, NKB><<<dim3((unsigned)pl.grid), SS_THREADS, pl.lds, st>>>(SS_PASS(p));
 }
 
-// Shapes / pointers were validated by the caller (v3_launch).
+// Shapes / pointers were validated by the caller (ll_w4a16_matmul_prepacked).
 int ss_launch(void* out, const void* x, const void* wpacked, const void* spacked, int64_t m, int64_t n, int64_t k, int group_size,
               int64_t x_stride_m, void* stream) {
   const SSPlan pl = ss_plan(m, n, k, group_size);
@@ -392,7 +359,7 @@ int ss_launch(void* out, const void* x, const void* wpacked, const void* spacked
   while ((128 << sh) < group_size) ++sh;
   p.gshift = sh;
   p.kb_base = pl.kb_base; p.kb_rem = pl.kb_rem; p.RB = pl.RB; p.total = pl.total; p.cap = pl.cap;
-  p.rb_magic = pl.RB > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)pl.RB - 1) / (uint64_t)pl.RB) : 0u;  // exact for item * RB < 2^32
+  p.rb_magic = ll_magic_u32(pl.RB);  // exact for item * RB < 2^32
   p.tl = nullptr;
   SS_DEBUG_SET(p)
   hipStream_t st = (hipStream_t)stream;

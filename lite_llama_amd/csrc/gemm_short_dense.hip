@@ -13,7 +13,8 @@
 #include <stdlib.h>
 
 #include "common.h"
-#include "gemm_w4_common.h"  // u32x4 / u32x2, v3_dma16, v3_vmcnt
+#include "gemm_engines.h"
+#include "gemm_w4_common.h"  // u32x4 / u32x2, v3_dma16, ll_wait_outstanding
 #include "gemm_w8_common.h"
 
 #define SD_CONSUMERS 8
@@ -36,20 +37,6 @@ struct SDParams {
   float* out;          // [S][M][N] fp32
   int x_stride;
 };
-
-__device__ __forceinline__ void sd_barrier() { asm volatile("s_barrier" ::: "memory"); }
-__device__ __forceinline__ void sd_wait_outstanding(int n) {  // at most n of this wave's memory operations still in flight
-  switch (n) {
-    case 0: v3_vmcnt<0>(); break;
-    case 2: v3_vmcnt<2>(); break;
-    case 4: v3_vmcnt<4>(); break;
-    case 6: v3_vmcnt<6>(); break;
-    case 8: v3_vmcnt<8>(); break;
-    case 12: v3_vmcnt<12>(); break;
-    case 16: v3_vmcnt<16>(); break;
-    default: v3_vmcnt<0>(); break;
-  }
-}
 
 // WF: 1 fp8 e4m3, 2 int8 (fp16 activations, block scales), 4 fp16, 5 bf16 weights (activations of the weight's type).
 // MT: 32-row batch halves; R: row groups per work item (8 / R k-interleaves per row group); P: pieces per consumer wave at most.
@@ -91,10 +78,10 @@ __global__ __launch_bounds__(SD_THREADS) void wssd_kernel(const SDParams p) {
 #pragma unroll
       for (int j = 0; j < PPL; ++j) v3_dma16<false>((uint32_t)(c * XT + (L * PPL + j) * 1024), xb + (size_t)c * 256, voff[j]);
     }
-    sd_wait_outstanding((nC - nC0) * PPL);
-    sd_barrier();  // A: chunks [0, nC0) of the slice are in LDS
+    ll_wait_outstanding((nC - nC0) * PPL);
+    ll_s_barrier();  // A: chunks [0, nC0) of the slice are in LDS
     v3_vmcnt<0>();
-    sd_barrier();  // B: all of it
+    ll_s_barrier();  // B: all of it
     return;
   }
 
@@ -172,10 +159,10 @@ __global__ __launch_bounds__(SD_THREADS) void wssd_kernel(const SDParams p) {
     }
   };
   f16x8 a0[4][MT], a1[4][MT];
-  sd_barrier();  // A
+  ll_s_barrier();  // A
 #pragma unroll
   for (int st = 0; st < 2; ++st) {
-    if (st == 1) sd_barrier();  // B
+    if (st == 1) ll_s_barrier();  // B
     read_x(a0, st * PH);
 #pragma unroll
     for (int i = 0; i < PH; ++i) {
@@ -233,17 +220,6 @@ struct SDPlan {
   int R = 0, S = 0, P = 0, kb_base = 0, kb_rem = 0, RB = 0, total = 0, cap = 0, grid = 0, lds = 0;
 };
 
-static int sd_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 static int sd_max_chunks(int kbs, int S) {  // most activation chunks any slice of the (kbs blocks, S slices) geometry touches
   const int base = kbs / S, rem = kbs % S;
   int worst = 0;
@@ -265,7 +241,7 @@ static SDPlan sd_plan(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits)
   const bool w16 = wfmt == 4 || wfmt == 5;
   if (off || (wfmt != 1 && wfmt != 2 && !w16) || m < 1 || m > 64 || n < 32 || n % 32 != 0 || k < 64 || k % 64 != 0) return best;
   if (n * k * (w16 ? 2 : 1) >= (1ll << 31) || (int64_t)(m - 1) * k * 2 + k * 2 >= (1ll << 31)) return best;  // 32-bit offsets
-  const int cus = sd_num_cus();
+  const int cus = ll_num_cus();
   const int rgs = (int)(n / 32), kbs = (int)(k / 64);
   const int mt = m > 32 ? 2 : 1;
   const double piece_kb = w16 ? 4.0 : 2.0;
@@ -320,13 +296,7 @@ int sd_partials_slices(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits
 
 template <int WF, int MT, int R, int P>
 static void sd_go(const SDParams& p, const SDPlan& pl, hipStream_t st) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)wssd_kernel<WF, MT, R, P>, hipFuncAttributeMaxDynamicSharedMemorySize, SD_MAX_CHUNKS * 2 * 32 * 256);
-    attr_set[dev] = true;
-  }
+  ll_lds_opt_in<wssd_kernel<WF, MT, R, P>>(SD_MAX_CHUNKS * 2 * 32 * 256);
   wssd_kernel<WF, MT, R, P><<<dim3((unsigned)pl.grid), SD_THREADS, pl.lds, st>>>(p);
 }
 

@@ -20,6 +20,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_engines.h"
 #include "gemm_w4_common.h"
 
 #define SF_CONSUMERS 8
@@ -38,9 +39,8 @@ struct SFParams {
   int total;            // work items = (N / 32 / R) * halves
 };
 
-__device__ __forceinline__ void sf_barrier() { asm volatile("s_barrier" ::: "memory"); }
-
-// at most `n` of this wave's memory operations may still be in flight
+// at most `n` (any count up to 40) of this wave's memory operations may still be in flight -- not ll_wait_outstanding, whose
+// seven-case table the other engines' kernels are compiled with
 __device__ __forceinline__ void sf_wait_outstanding(int n) {
   n = __builtin_amdgcn_readfirstlane(n);
 #define SF_C(N) case N: v3_vmcnt<N>(); break;
@@ -99,7 +99,7 @@ __global__ __launch_bounds__(SF_THREADS) void wsf_kernel(const SFParams p) {
       int need = (i + 1) * CPR;
       if (need > nC) need = nC;
       sf_wait_outstanding((issued - need) * PPL);
-      sf_barrier();  // B_i: round i may be read; round i - 1 has been read
+      ll_s_barrier();  // B_i: round i may be read; round i - 1 has been read
       if (i >= 1) {  // refill the slots of round i - 1
         int hi = (i - 1) * CPR + NSLOT + CPR;
         if (hi > nC) hi = nC;
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(SF_THREADS) void wsf_kernel(const SFParams p) {
   for (int i = 0; i < P; ++i) {
     if (i < rounds) {  // (wave-uniform, no early exit: the loop unrolls and the weight registers keep static indices; every wave of
                        //  the workgroup passes the same number of barriers)
-    sf_barrier();  // B_i
+    ll_s_barrier();  // B_i
     const int kk = i * KQ + q;
     const bool valid = kk < nkb;
     const int kb = valid ? kk : i * KQ;  // a piece past K: landed data of this round x exact zeros
@@ -231,17 +231,6 @@ struct SFPlan {
   int ok = 0, R = 0, MT = 0, halves = 0, P = 0, total = 0;
 };
 
-static int sf_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // The plan: one round of workgroups; 32-row batch halves when they fit (half the activation bytes per CU), else the whole batch
 // per item; R = 1 when the row groups fit, else 2.  Not served: wide outputs (the row-group engine / unit loop stream those),
 // K beyond what a wave's registers hold (16 pieces), an output fed by fewer than 16 row groups (nothing to spread).
@@ -249,7 +238,7 @@ static SFPlan sf_plan(int64_t m, int64_t n, int64_t k, int group_size) {
   SFPlan pl;
   static const int on = getenv("LL_GEMM_SF") ? atoi(getenv("LL_GEMM_SF")) : 1;  // A/B knob, read once (0: off)
   if (!on || !ll_w4a16_prepacked_supported(m, n, k, group_size) || m > 64) return pl;
-  const int cus = sf_num_cus();
+  const int cus = ll_num_cus();
   const int rgs = (int)(n / 32), nkb = (int)(k / 64);
   if (rgs < 16) return pl;
   // candidates in order of preference: batch halves first (half the activation bytes per CU, 8-KB tiles: the ring runs 3 - 8 rounds
@@ -271,11 +260,7 @@ static SFPlan sf_plan(int64_t m, int64_t n, int64_t k, int group_size) {
   return pl;
 }
 
-int sf_wants(int64_t m, int64_t n, int64_t k, int group_size, int epilogue) {
-  if ((epilogue >> 8) & 3) return 0;  // a forced unit-loop tile width (tests / tuning)
-  if ((epilogue & 3) == 2) return 0;  // split-K planes: gemm_short.hip
-  return sf_plan(m, n, k, group_size).ok;
-}
+int sf_wants(int64_t m, int64_t n, int64_t k, int group_size) { return sf_plan(m, n, k, group_size).ok; }
 
 // Host-side introspection (tests, notebook; no device work): [0] 1 if this engine takes the finished-output launch, [1] work items
 // (= grid), [2] R, [3] batch tiles per item, [4] batch halves, [5] pieces per wave (template bound), [6] ring slots, [7] LDS bytes.
@@ -290,17 +275,11 @@ extern "C" int ll_w4a16_short_full_plan(int64_t m, int64_t n, int64_t k, int gro
 
 template <int MT, int R, int P>
 static void sf_go(const SFParams& p, hipStream_t st) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)wsf_kernel<MT, R, P>, hipFuncAttributeMaxDynamicSharedMemorySize, SF_LDS_BYTES);
-    attr_set[dev] = true;
-  }
+  ll_lds_opt_in<wsf_kernel<MT, R, P>>(SF_LDS_BYTES);
   wsf_kernel<MT, R, P><<<dim3((unsigned)p.total), SF_THREADS, SF_LDS_BYTES, st>>>(p);
 }
 
-// Shapes / pointers were validated by the caller (v3_launch).
+// Shapes / pointers were validated by the caller (ll_w4a16_matmul_prepacked).
 int sf_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n, int64_t k,
               int group_size, int64_t x_stride_m, int epilogue, void* stream) {
   const SFPlan pl = sf_plan(m, n, k, group_size);

@@ -237,28 +237,10 @@ __global__ __launch_bounds__(R16_THREADS) __attribute__((amdgpu_waves_per_eu(2, 
   }
 }
 
-static int r16_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // the row-group loop needs R16Lds<MT>::BYTES of LDS per workgroup (160 KB at MT = 1): callers fall back when the device's opt-in
 // limit is smaller
 static bool r16_lds_fits(int64_t m) {
-  static int optin[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return true;  // no device (host-side plan queries): gfx950 assumed
-  if (!optin[dev]) {
-    int v = 0;
-    optin[dev] = hipDeviceGetAttribute(&v, hipDeviceAttributeSharedMemPerBlockOptin, dev) == hipSuccess && v > 0 ? v : 160 * 1024;
-  }
-  return (m <= 32 ? R16Lds<1>::BYTES : R16Lds<2>::BYTES) <= optin[dev];
+  return (m <= 32 ? R16Lds<1>::BYTES : R16Lds<2>::BYTES) <= ll_device_props().lds_optin;
 }
 
 extern "C" int ll_dense16_rows_supported(int64_t m, int64_t n, int64_t k, int epilogue) {
@@ -283,19 +265,13 @@ extern "C" int ll_dense16_rows_matmul(void* out, const void* x, const void* w, c
   p.chunks = (int)(k / 128);
   p.epi = epilogue;
   const int64_t rgs = n / 32;
-  int grid = r16_num_cus();
+  int grid = ll_num_cus();
   if (grid > rgs) grid = (int)rgs;
   p.rbase = (int)(rgs / grid); p.rrem = (int)(rgs % grid);
   hipStream_t st = (hipStream_t)stream;
 #define R16_GO(MT, DT)                                                                                                   \
   {                                                                                                                      \
-    static bool attr_[16] = {false}; /* per device */                                                   \
-    int dev_ = 0;                                                                                                        \
-    (void)hipGetDevice(&dev_);                                                                                           \
-    if (dev_ >= 0 && dev_ < 16 && !attr_[dev_]) {                                                                        \
-      (void)hipFuncSetAttribute((const void*)wgemm16_rows_kernel<MT, DT>, hipFuncAttributeMaxDynamicSharedMemorySize, R16Lds<MT>::BYTES); \
-      attr_[dev_] = true;                                                                                                \
-    }                                                                                                                    \
+    ll_lds_opt_in<wgemm16_rows_kernel<MT, DT>>(R16Lds<MT>::BYTES);                                                       \
     wgemm16_rows_kernel<MT, DT><<<dim3((unsigned)grid), R16_THREADS, R16Lds<MT>::BYTES, st>>>(p);                          \
   }
   if (m <= 32) {
@@ -333,19 +309,13 @@ extern "C" int ll_w8a8_rows_matmul(void* out, const int8_t* qa, const float* a_s
   p.chunks = (int)(k / 256);                                    // 256 bytes of a row per chunk
   p.epi = epilogue;
   const int64_t rgs = n / 32;
-  int grid = r16_num_cus();
+  int grid = ll_num_cus();
   if (grid > rgs) grid = (int)rgs;
   p.rbase = (int)(rgs / grid); p.rrem = (int)(rgs % grid);
   hipStream_t st = (hipStream_t)stream;
 #define R16_GO8(MT)                                                                                                      \
   {                                                                                                                      \
-    static bool attr_[16] = {false}; /* per device */                                                   \
-    int dev_ = 0;                                                                                                        \
-    (void)hipGetDevice(&dev_);                                                                                           \
-    if (dev_ >= 0 && dev_ < 16 && !attr_[dev_]) {                                                                        \
-      (void)hipFuncSetAttribute((const void*)wgemm16_rows_kernel<MT, R16_I8>, hipFuncAttributeMaxDynamicSharedMemorySize, R16Lds<MT>::BYTES); \
-      attr_[dev_] = true;                                                                                                \
-    }                                                                                                                    \
+    ll_lds_opt_in<wgemm16_rows_kernel<MT, R16_I8>>(R16Lds<MT>::BYTES);                                                   \
     wgemm16_rows_kernel<MT, R16_I8><<<dim3((unsigned)grid), R16_THREADS, R16Lds<MT>::BYTES, st>>>(p);                      \
   }
   if (m <= 32) R16_GO8(1) else R16_GO8(2)

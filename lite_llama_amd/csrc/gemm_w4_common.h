@@ -88,16 +88,16 @@ __device__ __forceinline__ void v3_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
-// host-side dispatch between the two engines (gemm_w4_v4.hip)
-extern "C" int ll_w4a16_prepacked_supported(int64_t m, int64_t n, int64_t k, int group_size);
-int v4_wants(int64_t m, int64_t n, int64_t k, int group_size, int epilogue);
-int v4_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n, int64_t k,
-              int group_size, int64_t x_stride_m, int epilogue, int kslices, void* stream);
-// ... and the short-stream engine for split-K partial launches of a few tens of KB per CU (gemm_short.hip)
-int ss_partials_slices(int64_t m, int64_t n, int64_t k, int group_size);  // planes it leaves; 0: not its launch
-// the short-stream engine with finished outputs (gemm_short_full.hip): narrow projections that must leave fp16 rows
-int sf_wants(int64_t m, int64_t n, int64_t k, int group_size, int epilogue);
-int sf_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n, int64_t k,
-              int group_size, int64_t x_stride_m, int epilogue, void* stream);
-int ss_launch(void* out, const void* x, const void* wpacked, const void* spacked, int64_t m, int64_t n, int64_t k, int group_size,
-              int64_t x_stride_m, void* stream);
+// at most `n` (0, 2, 4, 6, 8, 12 or 16) of this wave's memory operations may still be in flight; any other n waits for all
+__device__ __forceinline__ void ll_wait_outstanding(int n) {
+  switch (n) {
+    case 0: v3_vmcnt<0>(); break;
+    case 2: v3_vmcnt<2>(); break;
+    case 4: v3_vmcnt<4>(); break;
+    case 6: v3_vmcnt<6>(); break;
+    case 8: v3_vmcnt<8>(); break;
+    case 12: v3_vmcnt<12>(); break;
+    case 16: v3_vmcnt<16>(); break;
+    default: v3_vmcnt<0>(); break;
+  }
+}

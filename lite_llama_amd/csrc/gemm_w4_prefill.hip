@@ -280,16 +280,13 @@ extern "C" int ll_w4a16_matmul_prepacked_mtiled(void* out, const void* x, const 
   p.tiles_m = (int)((m + bm - 1) / bm);
   p.tiles_n = (int)(n / PF_BN);
   const int64_t grid = (int64_t)((p.tiles_m + 15) / 16) * ((p.tiles_n + 15) / 16) * 256;
-  static bool attr_set[16][2] = {{false}};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
   const int lds_bytes = PF_XR * bm * PF_BK * 2;
-  if (dev >= 0 && dev < 16 && !attr_set[dev][wmh - 1]) {
-    if (wmh == 2) (void)hipFuncSetAttribute((const void*)wgemm_prefill_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    else (void)hipFuncSetAttribute((const void*)wgemm_prefill_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-    attr_set[dev][wmh - 1] = true;
+  if (wmh == 2) {
+    ll_lds_opt_in<wgemm_prefill_kernel<2>>(lds_bytes);
+    wgemm_prefill_kernel<2><<<dim3((unsigned)grid), 512, lds_bytes, (hipStream_t)stream>>>(p);
+  } else {
+    ll_lds_opt_in<wgemm_prefill_kernel<1>>(lds_bytes);
+    wgemm_prefill_kernel<1><<<dim3((unsigned)grid), 256, lds_bytes, (hipStream_t)stream>>>(p);
   }
-  if (wmh == 2) wgemm_prefill_kernel<2><<<dim3((unsigned)grid), 512, lds_bytes, (hipStream_t)stream>>>(p);
-  else wgemm_prefill_kernel<1><<<dim3((unsigned)grid), 256, lds_bytes, (hipStream_t)stream>>>(p);
   return LL_LAUNCH_CHECK();
 }

@@ -32,6 +32,7 @@
 
 #include "common.h"
 #include "gemm_debug.h"  // V3_TL / V3_TLC / V3_TL_FENCE: in-kernel stamps of -DV3_TIMELINE builds (empty in the product build)
+#include "gemm_engines.h"
 #include "gemm_w4_common.h"
 
 #define V3_BN 128
@@ -192,7 +193,6 @@ __device__ __forceinline__ void v3_wait_units(int k) {
   else if (k == 3 || 4 * OPS > 63) v3_vmcnt<3 * OPS>();
   else v3_vmcnt<(4 * OPS > 63 ? 3 : 4) * OPS>();
 }
-__device__ __forceinline__ void v3_barrier() { asm volatile("s_barrier" ::: "memory"); }
 
 // One loader wave.  KIND 0: weight pieces 4L..4L+3 (1 KB each) + scale quarters 2L, 2L+1 (256 B each) of every
 // unit, V3_DW units ahead into a V3_RW-slot ring.  KIND 1: activation pieces 8L..8L+7 (4 rows x 256 B each),
@@ -253,7 +253,7 @@ __device__ __forceinline__ void v3_loader(const V3Params& p, const V3Seq& q, int
   for (int i = 0; i < pre; ++i) issue();
   V3_TL(2)
   v3_wait_units<OPS>(issued - 1);  // unit 0 has landed
-  v3_barrier();                    // P0
+  ll_s_barrier();                  // P0
   V3_TL(3)
   V3Walk cc = v3_walk_begin(q);
   int u0 = 0;
@@ -264,8 +264,8 @@ __device__ __forceinline__ void v3_loader(const V3Params& p, const V3Seq& q, int
     while (issued < fill) issue();
     const int need = cnt < 1 + AHEAD ? cnt : 1 + AHEAD;
     v3_wait_units<OPS>(issued - need);
-    v3_barrier();  // B0
-    if (v3_walk_ends(cc)) v3_barrier();  // k-half exchange (128-row tiles: one barrier)
+    ll_s_barrier();  // B0
+    if (v3_walk_ends(cc)) ll_s_barrier();  // k-half exchange (128-row tiles: one barrier)
     v3_walk_next(cc, q);
     u0 = 1;
   }
@@ -277,11 +277,11 @@ __device__ __forceinline__ void v3_loader(const V3Params& p, const V3Seq& q, int
     const int need = cnt < u + 1 + AHEAD ? cnt : u + 1 + AHEAD;
     v3_wait_units<OPS>(issued - need);
     if (u < 12) { V3_TL(5 + 3 * u) }
-    v3_barrier();
+    ll_s_barrier();
     if (u < 12) { V3_TL(6 + 3 * u) }
     if (v3_walk_ends(cc)) {  // the consumers' k-half exchange: 1 barrier, or 3 for 256-row tiles with two batch halves
       const int nb = NF == 1 ? 1 : (p.m > 32 ? 3 : 1);
-      for (int f = 0; f < nb; ++f) v3_barrier();
+      for (int f = 0; f < nb; ++f) ll_s_barrier();
     }
     v3_walk_next(cc, q);
   }
@@ -693,14 +693,14 @@ __global__ __launch_bounds__(V3_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
   int seg_lo = cc.c;
   int wnext = LD::OFF_W + RG::RA * LD::W_SLOT, xnext = LD::OFF_X + RG::RA * V3_X_SLOT;  // ring slots of the next unit to READ
   V3Ops<MT, NF> opA, opB;
-  v3_barrier();  // P0: unit 0 has landed
+  ll_s_barrier();  // P0: unit 0 has landed
   V3_TL(3)
   if constexpr (RG::RA) {
     // first step: unit 0 is multiplied as soon as it is there (its operands are read now, not one unit ahead); the loaders
     // meet the consumers again at B0 with units <= 2 landed, and the steady loop starts at unit 1
     read_ops(opA, LD::OFF_W, LD::OFF_X);
     compute(opA);
-    v3_barrier();  // B0
+    ll_s_barrier();  // B0
     V3_TL(4)
     const bool se0 = v3_walk_ends(cc);
     if (se0) segment_end(cc.t, seg_lo, cc.c);
@@ -730,7 +730,7 @@ __global__ __launch_bounds__(V3_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     if constexpr (!RG::RA) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); /* the slot is free once the barrier is passed */ \
     V3_TL_FENCE(CUR)                                                                        \
     if (done == 5) { V3_TLC(46) }                                                           \
-    v3_barrier();                                                                           \
+    ll_s_barrier();                                                                         \
     if (done == 5) { V3_TLC(47) }                                                           \
     if (done < 40) { V3_TL(4 + done) }                                                      \
     if (pending) post_pending(); /* the previous segment's slab stores are a unit old */    \
@@ -898,21 +898,10 @@ static const V3Knobs& v3_knobs() {
   return k;
 }
 
-static int v3_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 static V3Plan v3_plan(int64_t n, int64_t k, int nf_force = 0, bool partials = false) {
   const V3Knobs& kn = v3_knobs();
   V3Plan pl;
-  const int target = kn.wgs > 0 ? kn.wgs : v3_num_cus();  // one persistent 12-wave workgroup per CU
+  const int target = kn.wgs > 0 ? kn.wgs : ll_num_cus();  // one persistent 12-wave workgroup per CU
   // 256-row tiles (one activation tile feeds two weight blocks: half the activation traffic and half the
   // per-unit overhead per weight byte) when there are enough of them to keep the split coarse; 128 otherwise
   pl.nf = (n % (2 * V3_BN) == 0 && n / (2 * V3_BN) >= target / 2) ? 2 : 1;
@@ -972,36 +961,17 @@ static V3Plan v3_plan(int64_t n, int64_t k, int nf_force = 0, bool partials = fa
   return pl;
 }
 
-static bool v3_shape_ok(int64_t m, int64_t n, int64_t k) {
+bool v3_shape_ok(int64_t m, int64_t n, int64_t k) {
   if (!((m >= 1) && (m <= V3_BM) && (n >= V3_BN) && (n % V3_BN == 0) && (k >= V3_CK) && (k % V3_CK == 0))) return false;
   return n * k / 2 < (1ll << 31) && n * (k / V3_CK) * 8 < (1ll << 31);  // 32-bit buffer offsets
 }
 
-extern "C" int ll_w4a16_prepacked_supported(int64_t m, int64_t n, int64_t k, int group_size) {
-  if (group_size <= 0 || group_size % 128 != 0 || k % group_size != 0) return 0;
-  const int gdiv = group_size / 128;
-  return v3_shape_ok(m, n, k) && ((gdiv & (gdiv - 1)) == 0) ? 1 : 0;
-}
-
 // Split-K partial mode (epilogue 2 of ll_w4a16_matmul_prepacked): number of fp32 partials [S][M][N] the launch
 // writes; 0 when the shape has too many tiles for the tile-group split (use the ordinary epilogue then).
-static int v3_partials_count(int64_t m, int64_t n, int64_t k, int group_size) {
+int v3_partials_count(int64_t m, int64_t n, int64_t k, int group_size) {
   if (!ll_w4a16_prepacked_supported(m, n, k, group_size)) return 0;
   const V3Plan pl = v3_plan(n, k, 1, true);
   return pl.gt >= 1 && pl.grid == pl.nblocks * pl.gt ? pl.gt : 0;
-}
-// `epilogue` = the value the launch will be given: bits 8-9 (a forced unit-loop tile width, tests / tuning) keep the launch off the
-// short-stream engine (gemm_short.hip), whose k-split differs from the unit loop's.
-extern "C" int ll_w4a16_partials_count_ex(int64_t m, int64_t n, int64_t k, int group_size, int epilogue) {
-  if (!ll_w4a16_prepacked_supported(m, n, k, group_size)) return 0;
-  if (!((epilogue >> 8) & 3)) {
-    const int s = ss_partials_slices(m, n, k, group_size);
-    if (s > 0) return s;
-  }
-  return v3_partials_count(m, n, k, group_size);
-}
-extern "C" int ll_w4a16_partials_count(int64_t m, int64_t n, int64_t k, int group_size) {
-  return ll_w4a16_partials_count_ex(m, n, k, group_size, 2);
 }
 
 // The launch plan of ll_w4a16_matmul_prepacked for (n, k, epilogue) as 16 ints -- host-side introspection for tests and
@@ -1015,7 +985,7 @@ extern "C" int ll_w4a16_v3_plan(int64_t m, int64_t n, int64_t k, int group_size,
   const V3Plan pl = v3_plan(n, k, (epilogue >> 8) & 3, partials);
   const int v[16] = {pl.grid, pl.nf, pl.nblocks, pl.chunks, pl.slots, pl.gt, pl.gbase, pl.grem, pl.glead,
                      (partials && pl.gt >= 1 && pl.grid == pl.nblocks * pl.gt) ? pl.xcd_shift : -1, pl.upw, 0, 0,
-                     0, 0, v3_knobs().wgs > 0 ? v3_knobs().wgs : v3_num_cus()};
+                     0, 0, v3_knobs().wgs > 0 ? v3_knobs().wgs : ll_num_cus()};
   for (int i = 0; i < 16; ++i) out16[i] = v[i];
   return LL_OK;
 }
@@ -1034,28 +1004,11 @@ extern "C" int ll_w4a16_v3_workspace(int64_t m, int64_t n, int64_t k, int64_t* f
   return LL_OK;
 }
 
-static int v3_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n,
-                     int64_t k, int group_size, int64_t x_stride_m, float* workspace, int32_t* counters, int epilogue,
-                     void* stream) {
-  if (m < 0 || n <= 0 || k <= 0 || group_size <= 0) return LL_ERR_SHAPE;
-  if (m == 0) return LL_OK;
-  if (!ll_w4a16_prepacked_supported(m, n, k, group_size) || x_stride_m % 8 != 0 || ((epilogue & 1) && (n & 1))) return LL_ERR_SHAPE;
-  if (!out || !x || !wpacked || !spacked || !workspace || !counters) return LL_ERR_ARG;
-  if (!ll_aligned16(x) || !ll_aligned16(wpacked) || !ll_aligned16(spacked)) return LL_ERR_ARG;
-  if ((m - 1) * x_stride_m * 2 + k * 2 >= (1ll << 31)) return LL_ERR_SHAPE;
+// Validated and routed here by ll_w4a16_matmul_prepacked (gemm_w4_dispatch.hip).
+int v3_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n, int64_t k,
+              int group_size, int64_t x_stride_m, float* workspace, int32_t* counters, int epilogue, void* stream) {
   const bool partials = (epilogue & 3) == 2;
-  if (partials && (bias || !v3_partials_count(m, n, k, group_size))) return LL_ERR_SHAPE;
-  // round 6: split-K partial launches whose stream is a few tens of KB per CU run on the short-stream engine (gemm_short.hip)
-  if (partials && !((epilogue >> 8) & 3) && ss_partials_slices(m, n, k, group_size) > 0)
-    return ss_launch(out, x, wpacked, spacked, m, n, k, group_size, x_stride_m, stream);
-  // ... and narrow FINISHED outputs (the reference-shaped layer's q / k|v / o calls, the fused gate|up of a TP >= 4 shard) on its
-  // all-of-K form (gemm_short_full.hip): the sums meet inside the workgroup, no slabs, no counters
-  if (!partials && !v4_wants(m, n, k, group_size, epilogue) && sf_wants(m, n, k, group_size, epilogue))
-    return sf_launch(out, x, wpacked, spacked, bias, m, n, k, group_size, x_stride_m, epilogue, stream);
   const V3Plan pl = v3_plan(n, k, (epilogue >> 8) & 3, partials);
-  // round 5: the row-group engine (gemm_w4_v4.hip) takes the launch when its plan serves the shape -- same layouts, same planes
-  if (v4_wants(m, n, k, group_size, epilogue))
-    return v4_launch(out, x, wpacked, spacked, bias, m, n, k, group_size, x_stride_m, epilogue & 3, partials ? pl.gt : 1, stream);
   epilogue &= 3;
   V3Params p{};
   p.out = (uint16_t*)out; p.x = (const uint16_t*)x; p.wp = wpacked; p.sp = spacked; p.bias = (const uint16_t*)bias;
@@ -1068,29 +1021,22 @@ static int v3_launch(void* out, const void* x, const void* wpacked, const void* 
   p.nblocks = pl.nblocks; p.chunks = pl.chunks; p.total_units = pl.total_units; p.upw = pl.upw; p.slots = pl.slots;
   p.gt = pl.gt; p.gbase = pl.gbase; p.grem = pl.grem; p.glead = pl.glead;
   p.epi = epilogue;
-  auto magic = [](int d) { return d > 1 ? (uint32_t)(((1ull << 32) + (uint64_t)d - 1) / (uint64_t)d) : 0u; };
   // umulhi(x, ceil(2^32 / d)) == x / d for x * d < 2^32 (x: unit / workgroup indices); d == 1 is handled by the guard below
   if ((int64_t)pl.total_units * (pl.chunks > pl.upw ? pl.chunks : pl.upw) >= (1ll << 31)) return LL_ERR_SHAPE;
   p.err_idx = (int)(n / V3_BN * 8);
   p.xcd_shift = (partials && pl.gt >= 1 && pl.grid == pl.nblocks * pl.gt) ? pl.xcd_shift : -1;
-  p.chunks_magic = magic(pl.chunks);
-  p.gt_magic = magic(pl.gt);
-  p.upw_magic = magic(pl.upw);
+  p.chunks_magic = ll_magic_u32(pl.chunks);
+  p.gt_magic = ll_magic_u32(pl.gt);
+  p.upw_magic = ll_magic_u32(pl.upw);
   V3_DEBUG_SET(p)
   int sh = 0;
   while ((128 << sh) < group_size) ++sh;
   p.gshift = sh;
   hipStream_t st = (hipStream_t)stream;
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)wgemm3_kernel<1, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, V3Lds<1>::BYTES);
-    (void)hipFuncSetAttribute((const void*)wgemm3_kernel<2, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, V3Lds<1>::BYTES);
-    (void)hipFuncSetAttribute((const void*)wgemm3_kernel<1, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, V3Lds<2>::BYTES);
-    (void)hipFuncSetAttribute((const void*)wgemm3_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, V3Lds<2>::BYTES);
-    attr_set[dev] = true;
-  }
+  ll_lds_opt_in<wgemm3_kernel<1, 1>>(V3Lds<1>::BYTES);
+  ll_lds_opt_in<wgemm3_kernel<2, 1>>(V3Lds<1>::BYTES);
+  ll_lds_opt_in<wgemm3_kernel<1, 2>>(V3Lds<2>::BYTES);
+  ll_lds_opt_in<wgemm3_kernel<2, 2>>(V3Lds<2>::BYTES);
   const dim3 grid((unsigned)pl.grid);
   if (pl.nf == 2) {
     if (m <= 32) wgemm3_kernel<1, 2><<<grid, V3_THREADS, V3Lds<2>::BYTES, st>>>(p);
@@ -1100,11 +1046,4 @@ static int v3_launch(void* out, const void* x, const void* wpacked, const void* 
     else wgemm3_kernel<2, 1><<<grid, V3_THREADS, V3Lds<1>::BYTES, st>>>(p);
   }
   return LL_LAUNCH_CHECK();
-}
-
-extern "C" int ll_w4a16_matmul_prepacked(void* out, const void* x, const void* wpacked, const void* spacked,
-                                         const void* bias, int64_t m, int64_t n, int64_t k, int group_size,
-                                         int64_t x_stride_m, float* workspace, int32_t* counters, int epilogue,
-                                         void* stream) {
-  return v3_launch(out, x, wpacked, spacked, bias, m, n, k, group_size, x_stride_m, workspace, counters, epilogue, stream);
 }

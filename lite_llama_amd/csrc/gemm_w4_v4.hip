@@ -21,6 +21,7 @@
 
 #include "common.h"
 #include "gemm_debug.h"  // V4_TL: in-kernel stamps of -DV4_TIMELINE builds (empty in the product build)
+#include "gemm_engines.h"
 #include "gemm_w4_common.h"
 
 #define V4_THREADS 768
@@ -81,7 +82,6 @@ struct V4Params {
   V4_DEBUG_FIELDS
 };
 
-__device__ __forceinline__ void v4_barrier() { asm volatile("s_barrier" ::: "memory"); }
 template <int N> struct V4Int { static constexpr int value = N; };
 
 // s_waitcnt vmcnt(n) for a wave-uniform run-time n (the loaders' operation count per unit depends on the workgroup's row
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(V4_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     const int pre = cnt < V4_AHEAD ? cnt : V4_AHEAD;
     for (int i = 0; i < pre; ++i) issue();
     v3_vmcnt<0>();
-    v4_barrier();  // P0
+    ll_s_barrier();  // P0
     V4_TL(1)
     for (int u = 0; u < cnt; ++u) {
       const int want = cnt < u + R ? cnt : u + R;  // the slot of unit u - 1 is free since the barrier that ended it
@@ -215,10 +215,10 @@ __global__ __launch_bounds__(V4_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
       const int need = cnt < u + 1 + V4_AHEAD ? cnt : u + 1 + V4_AHEAD;
       v4_vmcnt_dyn((issued - need) * ops);
       if (u < 14) { V4_TL(3 + 4 * u) }
-      v4_barrier();  // B_u
+      ll_s_barrier();  // B_u
       if (u < 14) { V4_TL(4 + 4 * u) }
     }
-    v4_barrier();  // the consumers' k-quarter exchange
+    ll_s_barrier();  // the consumers' k-quarter exchange
     V4_TL(61)
     return;
   }
@@ -282,7 +282,7 @@ __global__ __launch_bounds__(V4_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
     int ws_cur = LD::OFF_W, xs_cur = LD::OFF_X;
     Ops opA, opB;
     f16x8 x0[MT], x1[MT];
-    v4_barrier();  // P0: units 0 and 1 have landed
+    ll_s_barrier();  // P0: units 0 and 1 have landed
     V4_TL(1)
     read_ws(opA, ws_cur);
     read_x(x0, xs_cur, 0);
@@ -312,7 +312,7 @@ __global__ __launch_bounds__(V4_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
         }                                                                                                   \
       }                                                                                                     \
       __builtin_amdgcn_sched_barrier(0);                                                                    \
-      v4_barrier();                                                                                         \
+      ll_s_barrier();                                                                                       \
       if (u < 14) { V4_TL(4 + 4 * u) }                                                                      \
       ws_cur = ws_n;                                                                                        \
       xs_cur = xs_n;                                                                                        \
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(V4_THREADS) __attribute__((amdgpu_waves_per_eu(3, 3
   if (par == 0) consume(V4Int<NA>{});
   else consume(V4Int<(NRGT - NA > 0 ? NRGT - NA : 1)>{});
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  v4_barrier();  // ... then the eight waves finish fragments w, w + 8, ...
+  ll_s_barrier();  // ... then the eight waves finish fragments w, w + 8, ...
   V4_TL(60)
 
   auto swap32 = [](uint32_t& a, uint32_t& bb) {  // lanes h = 1 of `a` <-> lanes h = 0 of `bb`
@@ -457,20 +457,9 @@ static const V4Knobs& v4_knobs() {
   return k;
 }
 
-static int v4_num_cus() {
-  static int cus[16] = {0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 256;
-  if (!cus[dev]) {
-    hipDeviceProp_t prop;
-    cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return cus[dev];
-}
-
 // row groups per workgroup of a finished-output launch; 0: not served here
 static int v4_full_nrgt(int64_t n) {
-  const int cus = v4_num_cus();
+  const int cus = ll_num_cus();
   const int64_t rgs = n / 32;
   const int per = (int)((rgs + cus - 1) / cus);
   if (rgs < (int64_t)v4_knobs().min_fill * cus) {
@@ -483,9 +472,7 @@ static int v4_full_nrgt(int64_t n) {
   return (per == 2 || per == 4 || per == 5) ? per : 0;
 }
 
-int v4_wants(int64_t m, int64_t n, int64_t k, int group_size, int epilogue) {
-  (void)m; (void)k; (void)group_size;
-  if ((epilogue >> 8) & 3) return 0;  // a forced v3 tile width (tests / tuning)
+int v4_wants(int64_t n, int epilogue) {
   const int epi = epilogue & 3;
   const V4Knobs& kn = v4_knobs();
   if (epi == 2) return (kn.on & 2) ? 1 : 0;
@@ -501,10 +488,10 @@ extern "C" int ll_w4a16_v4_plan(int64_t m, int64_t n, int64_t k, int group_size,
   if (!ll_w4a16_prepacked_supported(m, n, k, group_size)) return LL_ERR_SHAPE;
   for (int i = 0; i < 8; ++i) out8[i] = 0;
   const int nrgt = ((epilogue & 3) == 2) ? 0 : v4_full_nrgt(n);
-  out8[5] = v4_num_cus();
-  if (!nrgt || !v4_wants(m, n, k, group_size, epilogue)) return LL_OK;
+  out8[5] = ll_num_cus();
+  if (!nrgt || w4a16_engine(m, n, k, group_size, epilogue) != W4_ROW_GROUPS) return LL_OK;
   const int rgs = (int)(n / 32);
-  int ntiles = v4_num_cus();
+  int ntiles = ll_num_cus();
   if (ntiles > rgs) ntiles = rgs;
   out8[0] = 1; out8[1] = ntiles; out8[2] = nrgt; out8[3] = rgs / ntiles; out8[4] = rgs % ntiles;
   out8[6] = nrgt == 2 ? V4Lds<2>::BYTES : nrgt == 4 ? V4Lds<4>::BYTES : V4Lds<5>::BYTES;
@@ -513,17 +500,11 @@ extern "C" int ll_w4a16_v4_plan(int64_t m, int64_t n, int64_t k, int group_size,
 
 template <int NRGT, int MT>
 static void v4_go(const V4Params& p, int grid, hipStream_t st) {
-  static bool attr_set[16] = {false};
-  int dev = 0;
-  (void)hipGetDevice(&dev);
-  if (dev >= 0 && dev < 16 && !attr_set[dev]) {
-    (void)hipFuncSetAttribute((const void*)wgemm4_kernel<NRGT, MT>, hipFuncAttributeMaxDynamicSharedMemorySize, V4Lds<NRGT>::BYTES);
-    attr_set[dev] = true;
-  }
+  ll_lds_opt_in<wgemm4_kernel<NRGT, MT>>(V4Lds<NRGT>::BYTES);
   wgemm4_kernel<NRGT, MT><<<dim3((unsigned)grid), V4_THREADS, V4Lds<NRGT>::BYTES, st>>>(p);
 }
 
-// Shapes were validated by the caller (v3_launch); kslices = the k-split of the partial mode (= ll_w4a16_partials_count).
+// Shapes were validated by the caller (ll_w4a16_matmul_prepacked); kslices = the k-split of the partial mode (= ll_w4a16_partials_count).
 int v4_launch(void* out, const void* x, const void* wpacked, const void* spacked, const void* bias, int64_t m, int64_t n, int64_t k,
               int group_size, int64_t x_stride_m, int epilogue, int kslices, void* stream) {
   V4Params p{};
@@ -544,7 +525,7 @@ int v4_launch(void* out, const void* x, const void* wpacked, const void* spacked
   } else {
     nrgt = v4_full_nrgt(n);
     if (!nrgt) return LL_ERR_SHAPE;
-    ntiles = v4_num_cus();
+    ntiles = ll_num_cus();
     if (ntiles > rgs) ntiles = rgs;
     p.rbase = rgs / ntiles; p.rrem = rgs % ntiles;
     p.ks = 1;

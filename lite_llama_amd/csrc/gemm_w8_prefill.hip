@@ -17,6 +17,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_engines.h"
 #include "gemm_w4_common.h"
 #include "gemm_w8_common.h"
 
@@ -319,16 +320,10 @@ extern "C" int ll_w8_mtiled_try(void* out, const void* x, const void* w, const f
   p.tiles_n = (int)((n + P8_BN - 1) / P8_BN);
   const int64_t grid = (int64_t)((p.tiles_m + 15) / 16) * ((p.tiles_n + 15) / 16) * 256;
   hipStream_t st = (hipStream_t)stream;
-  int dev = 0;
-  (void)hipGetDevice(&dev);
 #define P8_GO(WF, WH, WROWB)                                                                                              \
   {                                                                                                                       \
     const int bytes_ = 2 * (WH * 128 * 128 + 256 * WROWB);                                                                \
-    static bool attr_[16] = {false};                                                                                      \
-    if (dev >= 0 && dev < 16 && !attr_[dev]) {                                                                            \
-      (void)hipFuncSetAttribute((const void*)w8_mtiled_kernel<WF, WH>, hipFuncAttributeMaxDynamicSharedMemorySize, bytes_); \
-      attr_[dev] = true;                                                                                                  \
-    }                                                                                                                     \
+    ll_lds_opt_in<w8_mtiled_kernel<WF, WH>>(bytes_);                                                                      \
     w8_mtiled_kernel<WF, WH><<<dim3((unsigned)grid), WH * 256, bytes_, st>>>(p);                                          \
   }
   if (wmh == 2) {

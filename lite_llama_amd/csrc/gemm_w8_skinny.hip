@@ -14,6 +14,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_engines.h"
 #include "gemm_w8_common.h"
 
 namespace {
@@ -387,11 +388,6 @@ extern "C" int ll_dense16_matmul(void* out, const void* x, const void* w, const 
 // ll_skip_rmsnorm_q8, ll_w8a8_finish_swiglu (w8a8_fused.hip).  Returns the number of planes written (>= 1), 0 when the
 // shape is not served, < 0 on error.
 // ---------------------------------------------------------------------------------------------------------------- //
-// the short-stream form of this mode (gemm_short_dense.hip): launches of a few tens of KB per CU
-int sd_partials_slices(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits);
-int sd_launch(float* out, const void* x, const void* w, const float* scales, int64_t m, int64_t n, int64_t k, int group_n,
-              int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride_bytes, int64_t s_stride_n, int64_t s_stride_k,
-              int max_splits, void* stream);
 
 extern "C" int ll_dense_partials_count(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits) {
   const bool w16 = wfmt == D8_F16 || wfmt == D8_BF16;

@@ -26,6 +26,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gemm_engines.h"
 
 #define GEMM_BN 128        // output columns (weight rows) per workgroup tile: 4 waves x 32
 #define GEMM_BM 64         // activation rows per tile (2 MFMA tiles)
@@ -607,25 +608,13 @@ struct Plan {
   int mblocks, nblocks, chunks, total_units, upw, grid, slots;
 };
 
-static int num_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      cus = prop.multiProcessorCount;
-    if (cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
 static Plan make_plan(int64_t m, int64_t n, int64_t k) {
   Plan pl;
   pl.mblocks = (int)((m + GEMM_BM - 1) / GEMM_BM);
   pl.nblocks = (int)((n + GEMM_BN - 1) / GEMM_BN);
   pl.chunks = (int)((k + GEMM_CK - 1) / GEMM_CK);
   pl.total_units = pl.mblocks * pl.nblocks * pl.chunks;
-  int target = 2 * num_cus();  // ~2 persistent workgroups per CU
+  int target = 2 * ll_num_cus();  // ~2 persistent workgroups per CU
   if (const char* e = getenv("LL_GEMM_WGS")) {  // tuning knob
     const int v = atoi(e);
     if (v > 0) target = v;
@@ -642,19 +631,6 @@ static Plan make_plan(int64_t m, int64_t n, int64_t k) {
   pl.slots = slots;
   return pl;
 }
-
-extern "C" int ll_w4a16_v3_workspace(int64_t m, int64_t n, int64_t k, int64_t* floats, int64_t* ints);  // gemm_w4_v3.hip
-
-// the decode-shaped 8-bit engine (gemm_w8_skinny.hip): served shapes leave S fp32 / int32 partial planes in the workspace
-extern "C" int64_t ll_dense8_partial_words(int64_t m, int64_t n, int64_t k);
-extern "C" int64_t ll_dense16_partial_words(int64_t m, int64_t n, int64_t k);
-extern "C" int ll_w8_mtiled_try(void* out, const void* x, const void* w, const float* scales, const float* a_scale, const void* bias,
-                                int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n, int64_t group_k, int wfmt,
-                                int64_t x_stride, int64_t w_stride, int64_t s_stride_n, int64_t s_stride_k, void* stream);  // gemm_w8_prefill.hip
-extern "C" int ll_dense8_try(void* out, const void* x, const void* w, const float* scales, const float* a_scale,
-                             const void* bias, int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n,
-                             int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride, int64_t s_stride_n,
-                             int64_t s_stride_k, void* partials, void* stream);
 
 extern "C" int ll_gemm_workspace(int64_t m, int64_t n, int64_t k, int64_t* workspace_floats,
                                  int64_t* counter_ints) {
@@ -679,9 +655,7 @@ static int launch_wgemm(GemmParams& p, hipStream_t st) {
   p.total_units = pl.total_units;
   p.upw = pl.upw;
   p.slots = pl.slots;
-  p.gk_magic = p.group_k >= ((int64_t)1 << 31)
-                   ? 0u
-                   : (unsigned)((((uint64_t)1 << 32) + p.group_k - 1) / (uint64_t)p.group_k);
+  p.gk_magic = ll_magic_u32(p.group_k);
   if (!p.workspace || !p.counters) return LL_ERR_ARG;
   p.dbg_t = nullptr;
   if (const char* e = getenv("LL_GEMM_TRACE")) p.dbg_t = (unsigned long long*)strtoull(e, nullptr, 0);
