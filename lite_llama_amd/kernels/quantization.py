@@ -31,18 +31,16 @@ def _auto_prepacked(m, n, k, group_size, qweight, scales, zeros):
         return None
     if not w4a16_prepacked_supported(m, n, k, group_size):
         return None
-    key = (qweight.data_ptr(), qweight._version, scales.data_ptr(), scales._version, zeros.data_ptr(), zeros._version)
-    cached = getattr(qweight, "_ll_prepacked", None)
-    if cached is not None and cached[0] == key:
-        return cached[1]
-    if torch.cuda.is_current_stream_capturing():
-        return None
-    try:
-        pre = (pack_w4a16_weights(qweight), pack_w4a16_scales(scales, zeros))
-        qweight._ll_prepacked = (key, pre)
-    except (AttributeError, RuntimeError):
-        return None
-    return pre
+    from ..quantization.derived_layouts import keyed  # (here: the quantization package imports this module)
+
+    def build():
+        try:
+            return pack_w4a16_weights(qweight), pack_w4a16_scales(scales, zeros)
+        except (AttributeError, RuntimeError):
+            return None
+
+    return keyed(qweight, (qweight.data_ptr(), qweight._version, scales.data_ptr(), scales._version, zeros.data_ptr(),
+                           zeros._version), build)
 
 
 def w4a16_matmul(

@@ -11,6 +11,7 @@ import torch.nn as nn
 
 from .distributed.parallel_state import all_reduce_tp, collective_forced, divide, get_tp_world_size
 from .quantization import QuantConfig, get_linear_method
+from .quantization.derived_layouts import W4Layouts, drop_derived, holds_packed
 
 
 def _export_reference_weight(module, state_dict, prefix, local_metadata):
@@ -18,7 +19,7 @@ def _export_reference_weight(module, state_dict, prefix, local_metadata):
     layout (permuted words) -- the EXPORTED entry is the reference-format tensor, rebuilt transiently (bit-exact inverse
     permutation); the model itself is not touched, so captured graphs keep replaying over the packed storage.
     Covers ``model.state_dict()`` and any ``submodule.state_dict()`` alike."""
-    if getattr(module, "_w4_compact", False) or getattr(module, "_w4_compact_member", None) is not None:
+    if holds_packed(module):
         key = prefix + "weight"
         if key in state_dict:
             state_dict[key] = module.quant_method.reference_weight(module).detach()
@@ -27,8 +28,7 @@ def _export_reference_weight(module, state_dict, prefix, local_metadata):
 def _refuse_load_into_compact(module, state_dict, prefix, local_metadata, strict, missing_keys, unexpected_keys, error_msgs):
     """load_state_dict pre-hook: checkpoint rows copied into a parameter that aliases the load-time layout would be read as
     permuted words -- silently wrong.  ``CausalLM.load_state_dict`` expands first; a direct submodule load has to."""
-    if (getattr(module, "_w4_compact", False) or getattr(module, "_w4_compact_member", None) is not None) \
-            and (prefix + "weight") in state_dict:
+    if holds_packed(module) and (prefix + "weight") in state_dict:
         raise RuntimeError(f"{prefix}weight aliases the decode engine's load-time layout (compact_weights): call "
                            "model.expand_weights() before loading a checkpoint into it")
 
@@ -196,14 +196,14 @@ class MergedColumnLinear:
         first = self.layers[0]
         if not first.weight.is_cuda or torch.cuda.is_current_stream_capturing():
             return False
-        if any(getattr(l, "_w4_compact_member", None) is not None for l in self.layers):
-            # the members' `weight` parameters are views of the decode engine's layout, not reference rows: merging them again
-            # would permute garbage.  Somebody replaced a parameter of a compacted model.
+        for l in self.layers:  # a member compacted on its own holds permuted words: merge reference-format rows only
+            if hasattr(l.quant_method, "expand"):
+                l.quant_method.expand(l)
+        if any(holds_packed(l) for l in self.layers):
+            # members of a compacted holder: their `weight` parameters are views of the decode engine's layout, not reference
+            # rows, and merging them again would permute garbage.  Somebody replaced a parameter of a compacted model.
             raise RuntimeError("a parameter of a compacted merged projection was replaced: call model.expand_weights() before "
                                "loading or assigning weights (CausalLM.compact_weights keeps only the decode engine's layout)")
-        for l in self.layers:  # a member compacted on its own holds permuted words: merge reference-format rows only
-            if getattr(l, "_w4_compact", False):
-                l.quant_method.expand(l)
         self._holder = None
         ok = all(type(l.quant_method) is type(first.quant_method) and l.quant == first.quant
                  and l.input_size == first.input_size for l in self.layers)
@@ -237,30 +237,24 @@ class MergedColumnLinear:
                     ok = False
                     break
         if ok:
+            self._holder = holder
             for name, cat in merged.items():
                 setattr(holder, name, cat)
-                if cat is None:
-                    continue
-                off = 0
-                for i, l in enumerate(self.layers):
-                    rows = l._parameters[name].shape[0]
-                    view = cat[i::2] if il else cat[off:off + rows]
-                    l._parameters[name] = nn.Parameter(view, requires_grad=False)
-                    off += rows
-            self._holder = holder
+                if cat is not None:
+                    self._repoint_members(name)
         self._key = self._snapshot()
         return ok
 
-    def _repoint_members(self, name: str) -> None:
-        """Members' parameters are views of the holder's merged tensor: rebuild them after the tensor was replaced."""
+    def _repoint_members(self, name: str) -> list:
+        """Members' parameters are views of the holder's merged tensor: (re)build them; returns each member's rows of it."""
         h = self._holder
-        cat = getattr(h, name)
-        off = 0
+        cat, off, rows_of = getattr(h, name), 0, []
         for i, l in enumerate(self.layers):
-            rows = l._parameters[name].shape[0]
-            view = cat[i::2] if h.interleaved else cat[off:off + rows]
-            l._parameters[name] = nn.Parameter(view, requires_grad=False)
-            off += rows
+            n = l._parameters[name].shape[0]
+            rows_of.append(slice(i, None, 2) if h.interleaved else slice(off, off + n))
+            l._parameters[name] = nn.Parameter(cat[rows_of[-1]], requires_grad=False)
+            off += n
+        return rows_of
 
     def compact(self) -> int:
         """One resident copy of the merged int4 weights (quantization/methods.py::W4A16LinearMethod.compact): the holder's
@@ -273,39 +267,26 @@ class MergedColumnLinear:
             return 0
         freed = h.quant_method.compact(h)
         if freed:
-            off = 0
-            rows_of = []
-            for i, l in enumerate(self.layers):
-                rows = l._parameters["weight"].shape[0]
-                rows_of.append(slice(i, None, 2) if h.interleaved else slice(off, off + rows))
-                off += rows
-            self._repoint_members("weight")
-            for l, rows in zip(self.layers, rows_of):
-                l._w4_compact_member = (h, rows)
-                for attr in ("_w4_prepacked",):
-                    if hasattr(l, attr):
-                        delattr(l, attr)
+            for l, rows in zip(self.layers, self._repoint_members("weight")):
+                W4Layouts.of(l).member = (h, rows)
+                drop_derived(l)  # (its weight now views the holder's packed words)
             self._key = self._snapshot()
         return freed
 
     def expand(self) -> None:
         h = self._holder
-        if h is None or not getattr(h, "_w4_compact", False):
+        if not holds_packed(h):
             return
         h.quant_method.expand(h)
         self._repoint_members("weight")
         for l in self.layers:
-            if hasattr(l, "_w4_compact_member"):
-                delattr(l, "_w4_compact_member")
+            W4Layouts.of(l).member = None
         self._key = self._snapshot()
 
     def invalidate(self) -> None:
         """A checkpoint was copied THROUGH the members' parameters (views of the merged storage: the storage itself is up
         to date, no version counter moved): drop the layouts derived from it."""
-        if self._holder is not None:
-            for attr in ("_w4_prepacked", "_w4_packed"):
-                if hasattr(self._holder, attr):
-                    delattr(self._holder, attr)
+        drop_derived(self._holder)
 
     def __call__(self, x: torch.Tensor):
         """-> one output view per member (column blocks of the merged ``[..., sum N]`` result)."""

@@ -38,6 +38,7 @@ from .kernels import (
 )
 from .linear import ColumnParallelLinear, LinearBase, MergedColumnLinear, RowParallelLinear
 from .quantization import QuantConfig, get_moe_method
+from .quantization.derived_layouts import derived_tensors, holds_packed
 
 _LOG2E = 1.4426950408889634  # prefill kernel evaluates exp2 (base.py:45-47)
 
@@ -652,14 +653,9 @@ class CausalLM(nn.Module):
         the bytes released.
         ``state_dict()`` of a compacted model still exports the reference layouts (rebuilt per entry, nothing is mutated);
         ``expand_weights()`` undoes the compaction (``load_state_dict`` calls it first)."""
-        freed = 0
-        members = set()
-        for mc in self._merged_linears():
-            freed += mc.compact()
-            if getattr(mc._holder, "_w4_compact", False):
-                members.update(id(l) for l in mc.layers)
+        freed = sum(mc.compact() for mc in self._merged_linears())
         for m in self.modules():
-            if isinstance(m, LinearBase) and id(m) not in members and hasattr(m.quant_method, "compact"):
+            if isinstance(m, LinearBase) and hasattr(m.quant_method, "compact"):  # (members of a compacted holder: 0)
                 freed += m.quant_method.compact(m)
             if isinstance(m, SparseMoeBlock):
                 if m.interleave_gate_up_():  # (frees nothing: rows re-ordered for the fused epilogue; block scales GROW, see there)
@@ -671,9 +667,7 @@ class CausalLM(nn.Module):
 
     def is_compacted(self) -> bool:
         return any(getattr(m, "_gu_interleaved", False) for m in self.modules() if isinstance(m, SparseMoeBlock)) or \
-            any(getattr(m, "_w4_compact", False) or getattr(m, "_w4_compact_member", None) is not None
-                for m in self.modules() if isinstance(m, LinearBase)) or \
-            any(getattr(mc._holder, "_w4_compact", False) for mc in self._merged_linears())
+            any(holds_packed(m) for m in self.modules() if isinstance(m, LinearBase))  # (a compacted holder's members: too)
 
     # (state_dict(): the per-module post-hooks -- linear.py::_export_reference_weight, SparseMoeBlock._export_stacked_gate_up --
     # export reference layouts from a compacted model without touching it)
@@ -715,11 +709,7 @@ class CausalLM(nn.Module):
             add(p_)
         holders = [mc._holder for mc in self._merged_linears() if mc._holder is not None]
         for obj in list(self.modules()) + holders:
-            for name in ("_w4_prepacked", "_w4_packed"):
-                c = getattr(obj, name, None)
-                if c is not None:
-                    add(c[1])
-            for t in vars(obj).values():
+            for t in derived_tensors(obj) + list(vars(obj).values()):
                 add(t)
         return total
 

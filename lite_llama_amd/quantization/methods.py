@@ -20,6 +20,7 @@ from ..kernels.quantization import (dense16_linear, dense16_rows_linear, dense16
                                     w4a16_matmul_prepacked_rows, w4a16_mtiled_supported,
                                     w4a16_matmul_prepacked, w4a16_prepacked_supported)
 from .config import FP8, INT4, INT8, SMOOTHQUANT, QuantConfig
+from .derived_layouts import W4Layouts, keyed
 from .params import (
     quantize_fp8_per_channel,
     quantize_int4_groupwise,
@@ -121,44 +122,56 @@ class W4A16LinearMethod(LinearQuantMethod):
         return w4a16_matmul(x, self.reference_weight(layer), layer.weight_scale, layer.weight_zeros,
                             group_size=layer.quant.group_k, bias=layer.bias)
 
-    def _rows_layout(self, layer, x):
-        """The load-time layout for a call of MORE than 64 rows (``w4a16_matmul_prepacked_rows``): the compacted parameter
-        itself, the copy the decode engine already cached, or -- outside a graph capture -- a freshly packed one (kept, like the
-        decode engine's).  ``None`` -> the reference-layout engine (``LL_W4_NO_MTILED``, shapes off the 256-row grid, ...)."""
-        m = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if m <= 64 or os.environ.get("LL_W4_NO_MTILED") or not layer.weight.is_cuda:
-            return None
-        if getattr(layer, "_w4_compact_member", None) is not None:
-            return None
-        n, kp = layer.weight.shape
-        if not w4a16_mtiled_supported(m, n, kp * 8, layer.quant.group_k) or self._packed(layer) is None:
-            return None
-        if getattr(layer, "_w4_compact", False):
-            return self._as_packed(layer.weight.data)
-        key = (layer.weight.data_ptr(), layer.weight._version)
-        cached = getattr(layer, "_w4_prepacked", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        if torch.cuda.is_current_stream_capturing() or os.environ.get("LL_W4_NO_PREPACK"):
-            return None
-        pre = pack_w4a16_weights(layer.weight.data)
-        layer._w4_prepacked = (key, pre)
-        return pre
-
-    # ---- one resident copy of the int4 weights (round 4) ------------------------------------------------------------
     @staticmethod
     def _as_packed(t):
         n, kp = t.shape
         return t.view(n // 128, kp // 16, 8, 64, 4)
 
+    @staticmethod
+    def _set_weight(layer, t):
+        if isinstance(layer.weight, nn.Parameter):
+            layer.weight.data = t
+        else:
+            layer.weight = t
+
+    def _prepacked(self, layer, x):
+        """Decode-shaped calls (1..64 rows): the decode engine over :meth:`_packed_weight`; ``None`` -> another route."""
+        m = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        n, kp = layer.weight.shape
+        if 1 <= m <= 64 and layer.weight.is_cuda and w4a16_prepacked_supported(m, n, kp * 8, layer.quant.group_k):
+            return self._packed_weight(layer)
+        return None
+
+    def _rows_layout(self, layer, x):
+        """Calls of MORE than 64 rows: the M-tiled engine over the same layout; ``None`` -> the reference-layout engine."""
+        m = x.numel() // x.shape[-1] if x.shape[-1] else 0
+        n, kp = layer.weight.shape
+        if (m > 64 and not os.environ.get("LL_W4_NO_MTILED") and layer.weight.is_cuda
+                and w4a16_mtiled_supported(m, n, kp * 8, layer.quant.group_k)):
+            return self._packed_weight(layer)
+        return None
+
+    def _packed_weight(self, layer):
+        """The load-time layout of ``layer.weight`` (``pack_w4a16_weights``), served only when the scales pack too: the
+        parameter itself once compacted, else a copy cached next to it.  ``None`` for a member of a compacted merged storage
+        (called on its own: reference route over rebuilt rows) and, unless compacted, under ``LL_W4_NO_PREPACK``."""
+        rec = W4Layouts.of(layer)
+        if rec.member is not None or (os.environ.get("LL_W4_NO_PREPACK") and not rec.compact) or self._packed(layer) is None:
+            return None
+        if rec.compact:
+            return self._as_packed(layer.weight.data)
+        w = layer.weight
+        return keyed(rec, (w.data_ptr(), w._version), lambda: pack_w4a16_weights(w.data), "weight")
+
+    # ---- one resident copy of the int4 weights (round 4) ------------------------------------------------------------
     def reference_weight(self, layer):
         """``qweight [N, K/8]`` in the reference layout: the parameter itself -- or, for a compacted layer, a transient
         tensor rebuilt from the load-time layout (bit-exact inverse permutation, ``ll_w4a16_unpack_weights``)."""
-        member = getattr(layer, "_w4_compact_member", None)
-        if member is not None:  # a member of a compacted merged storage: its rows of the merged reference tensor
-            holder, rows = member
+        rec = W4Layouts.of(layer)
+        if rec.member is not None:  # a member of a compacted merged storage: its rows of the merged reference tensor
+            holder, rows = rec.member
             return self.reference_weight(holder)[rows].contiguous()
-        if getattr(layer, "_w4_compact", False):
+        if rec.compact:
             return unpack_w4a16_weights(self._as_packed(layer.weight.data))
         return layer.weight
 
@@ -169,36 +182,25 @@ class W4A16LinearMethod(LinearQuantMethod):
         for calls of more than 64 rows and for export.  Returns the bytes released (0: not served / already compact).
         ``state_dict()`` of a compacted model holds permuted words: call ``expand`` (or ``model.expand_weights()``) before
         saving or loading a checkpoint."""
-        if getattr(layer, "_w4_compact", False) or getattr(layer, "_w4_compact_member", None) is not None:
-            return 0
+        rec = W4Layouts.of(layer)
         w = layer.weight
         n, kp = w.shape
-        if (not w.is_cuda or os.environ.get("LL_W4_NO_PREPACK") or torch.cuda.is_current_stream_capturing()
-                or not w4a16_prepacked_supported(1, n, kp * 8, layer.quant.group_k) or self._packed(layer) is None):
+        if (rec.compact or not w.is_cuda or torch.cuda.is_current_stream_capturing()
+                or not w4a16_prepacked_supported(1, n, kp * 8, layer.quant.group_k)):
             return 0
-        cached = getattr(layer, "_w4_prepacked", None)
-        pre = cached[1] if cached is not None and cached[0] == (w.data_ptr(), w._version) else pack_w4a16_weights(w.data)
-        flat = pre.view(n, kp)
-        if isinstance(w, nn.Parameter):
-            w.data = flat
-        else:
-            layer.weight = flat
-        layer._w4_compact = True
-        layer._w4_prepacked = ((layer.weight.data_ptr(), layer.weight._version), pre)
+        pre = self._packed_weight(layer)
+        if pre is None:
+            return 0
+        self._set_weight(layer, pre.view(n, kp))
+        rec.compact, rec.weight = True, None  # (the parameter is the layout now)
         return n * kp * 4
 
     def expand(self, layer) -> None:
         """Undo :meth:`compact`: ``layer.weight`` is the reference-format tensor again (a fresh allocation)."""
-        if not getattr(layer, "_w4_compact", False):
-            return
-        ref = unpack_w4a16_weights(self._as_packed(layer.weight.data))
-        if isinstance(layer.weight, nn.Parameter):
-            layer.weight.data = ref
-        else:
-            layer.weight = ref
-        layer._w4_compact = False
-        if hasattr(layer, "_w4_prepacked"):
-            delattr(layer, "_w4_prepacked")
+        rec = W4Layouts.of(layer)
+        if rec.compact:
+            self._set_weight(layer, unpack_w4a16_weights(self._as_packed(layer.weight.data)))
+            rec.compact = False
 
     def apply_partials(self, layer, x, allow_bias: bool = False, max_splits: int = 12):
         """Decode-shaped projection left as fp32 split-K partials for ``skip_rmsnorm_partials`` /
@@ -230,42 +232,13 @@ class W4A16LinearMethod(LinearQuantMethod):
 
     @staticmethod
     def _packed(layer):
-        """Load-time re-layout of the scale/zero grids for the decode GEMM (extension; cached on the
-        layer, rebuilt if the parameters were replaced).  Not built inside a graph capture."""
-        key = (layer.weight_scale.data_ptr(), layer.weight_zeros.data_ptr(),
-               layer.weight_scale._version, layer.weight_zeros._version)
-        cached = getattr(layer, "_w4_packed", None)
-        if cached is not None and cached[0] == key:
-            return cached[1]
-        if not layer.weight_scale.is_cuda or torch.cuda.is_current_stream_capturing():
+        """Load-time re-layout of the scale/zero grids for the decode GEMM (extension; cached on the layer's record, rebuilt
+        if the parameters were replaced).  Not built inside a graph capture."""
+        s, z = layer.weight_scale, layer.weight_zeros
+        if not s.is_cuda:
             return None
-        packed = pack_w4a16_scales(layer.weight_scale.data, layer.weight_zeros.data)
-        layer._w4_packed = (key, packed)
-        return packed
-
-    def _prepacked(self, layer, x):
-        """Decode-shaped calls (<= 64 rows) stream the weights from their load-time layout
-        (``pack_w4a16_weights``; cached on the layer next to the reference-format parameter, which stays
-        the checkpoint-facing tensor and serves every other shape).  ``None`` -> reference-format path."""
-        n, kp = layer.weight.shape
-        m = x.numel() // x.shape[-1] if x.shape[-1] else 0
-        if getattr(layer, "_w4_compact_member", None) is not None:
-            return None  # (a member of a compacted merged storage called on its own: reference route over rebuilt rows)
-        if m < 1 or m > 64 or not layer.weight.is_cuda or (os.environ.get("LL_W4_NO_PREPACK") and not getattr(layer, "_w4_compact", False)):
-            return None
-        if not w4a16_prepacked_supported(m, n, kp * 8, layer.quant.group_k):
-            return None
-        if getattr(layer, "_w4_compact", False):  # the parameter IS the load-time layout
-            return self._as_packed(layer.weight.data) if self._packed(layer) is not None else None
-        key = (layer.weight.data_ptr(), layer.weight._version)
-        cached = getattr(layer, "_w4_prepacked", None)
-        if cached is not None and cached[0] == key:
-            return cached[1] if self._packed(layer) is not None else None
-        if torch.cuda.is_current_stream_capturing() or self._packed(layer) is None:
-            return None
-        pre = pack_w4a16_weights(layer.weight.data)
-        layer._w4_prepacked = (key, pre)
-        return pre
+        return keyed(W4Layouts.of(layer), (s.data_ptr(), z.data_ptr(), s._version, z._version),
+                     lambda: pack_w4a16_scales(s.data, z.data), "scales")
 
     def convert_from_fp16(self, layer, quant):
         qw, sc, zr = quantize_int4_groupwise(layer.weight.data, quant.group_k)

@@ -25,6 +25,7 @@ import torch.nn as nn
 
 from .distributed.parallel_state import get_tp_rank, get_tp_world_size
 from .distributed.partition import plan_range
+from .quantization.derived_layouts import drop_derived
 
 FP8_BLOCK = 128                     # block-fp8 checkpoints: one fp32 scale per 128 x 128 weights (weight_utils.py:58-71)
 SCALE_SUFFIX = "weight_scale_inv"
@@ -366,15 +367,10 @@ def invalidate_derived_layouts(model: nn.Module) -> None:
     """Drop every load-time layout derived from a parameter (the int4 decode engine's pre-packed weights / scale pairs,
     merged q|k|v and gate|up storages): ``view.copy_`` writes through ``param.data`` and bumps no version counter, so the
     caches' (pointer, version) keys cannot see a checkpoint loaded after a warm-up forward."""
-    for p_ in model.parameters():  # the drop-in route keeps its layouts ON the weight tensor (kernels/quantization.py::_auto_prepacked)
-        if hasattr(p_, "_ll_prepacked"):
-            delattr(p_, "_ll_prepacked")
-        if hasattr(p_.data, "_ll_prepacked"):
-            delattr(p_.data, "_ll_prepacked")
+    for obj in (*model.parameters(), *model.modules()):  # (the drop-in route keeps its layouts ON the weight tensor)
+        drop_derived(obj)
     for mod in model.modules():
-        for attr in ("_w4_prepacked", "_w4_packed", "_tp_fused_cache"):
-            if hasattr(mod, attr):
-                delattr(mod, attr)
+        vars(mod).pop("_tp_fused_cache", None)  # (the TP route's per-row-count agreement: re-decided after a load)
         for val in list(vars(mod).values()):
             if hasattr(val, "invalidate") and hasattr(val, "refresh"):
                 val.invalidate()

@@ -164,6 +164,50 @@ def test_quant_registry_and_layout():
         QuantConfig.for_runtime_scheme("int3")
 
 
+def test_derived_layout_cache_follows_the_source_version(monkeypatch):
+    """The keyed cache behind every int4 derived layout (quantization/derived_layouts.py), with a fake builder on CPU
+    tensors: reused under the same (data_ptr, _version) key, rebuilt after an in-place write, never built inside a graph
+    capture, and empty after the drop call -- on a layer's record and on a weight tensor alike."""
+    from lite_llama_amd.linear import LinearBase
+    from lite_llama_amd.quantization import QuantConfig
+    from lite_llama_amd.quantization.derived_layouts import W4Layouts, derived_tensors, drop_derived, keyed
+
+    capturing = [False]
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: capturing[0])
+    lin = LinearBase(256, 128, quant=QuantConfig.int4_groupwise(128))
+    w = lin.weight
+    built = []
+
+    def build():
+        built.append(w._version)
+        return w.detach().clone()
+
+    def lookup():
+        return keyed(W4Layouts.of(lin), (w.data_ptr(), w._version), build, "weight")
+
+    first = lookup()
+    assert lookup() is first and len(built) == 1
+    assert len(derived_tensors(lin)) == 1 and derived_tensors(lin)[0] is first
+    with torch.no_grad():
+        w.add_(1)  # in place: same pointer, the version counter moves
+    capturing[0] = True
+    assert lookup() is None and len(built) == 1  # stale, and no allocation inside a capture
+    capturing[0] = False
+    second = lookup()
+    assert second is not first and len(built) == 2 and torch.equal(second, w)
+    assert lookup() is second and len(built) == 2
+    drop_derived(lin)
+    assert derived_tensors(lin) == [] and W4Layouts.of(lin).weight is None
+    lookup()
+    assert len(built) == 3
+
+    key = (w.data_ptr(), w._version)  # the reference-signature route keeps its pair on the weight tensor
+    pair = keyed(w, key, lambda: (w + 1, w + 2))
+    assert keyed(w, key, lambda: None) is pair
+    drop_derived(w)
+    assert keyed(w, key, lambda: None) is None
+
+
 def test_quantisers_match_oracle_bit_exactly():
     from lite_llama_amd.quantization import (quantize_fp8_per_channel, quantize_int4_groupwise,
                                              quantize_int8_groupwise, quantize_int8_per_channel)
