@@ -13,14 +13,23 @@ int4 quantiser semantics, seeded random K/V for a 512-token context per sequence
 tokens; greedy, no EOS stop, lockstep batch -- the reference's measurement protocol
 (benchmarks/common.py:101-137).  Inputs are resident in HBM when the timed region starts.
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
-  roofline     -- dominant kernel (wgemm3_kernel = W4A16 dequant-GEMM): algorithmic weight bytes per
-                  launch / average launch duration measured live with HIP events, vs 8 TB/s HBM peak
-  cpu_baseline -- the reference's CPU-runnable case (benchmarks/bench_hf_baseline.py protocol: Qwen2.5-0.5B
-                  geometry, batch 1, 2 x 8-token warm-up, TTFT, TPOT, 256 generated tokens) on the host cores,
-                  plus "oracle_port": the CPU oracle on a slice of the headline workload (N = 1 only)
+Rank 0 prints ONE JSON line.  A plain run does only what the headline needs: set-up,
+warm-up, the timed steps, --dump-outputs, and the line (value, ms_per_step, config, step_roofline, memory) with
   graph        -- true when the timed steps were hipGraph replays; a refused capture is reported here (and on
                   stderr) together with "graph_error", never silently
+--full adds everything else the benchmark measures or checks, after the timed steps on rank 0 (most at N = 1 only):
+  secondary    -- the ctx-2048 point, then BASELINE.json configs 2 / 4 / 5, each in a process of its own
+  prefill      -- TTFT of the same workload
+  roofline     -- dominant kernel (wgemm3_kernel = W4A16 dequant-GEMM): algorithmic weight bytes per
+                  launch / average launch duration measured live with HIP events, vs 8 TB/s HBM peak,
+                  with counters of live rocprofv3 --pmc passes where available
+  reference_order, hbm, shard_sim -- the drop-in route, a device copy's bandwidth, TP shard shapes on one GPU
+  cpu_baseline -- the reference's CPU-runnable case (benchmarks/bench_hf_baseline.py protocol: Qwen2.5-0.5B
+                  geometry, batch 1, 2 x 8-token warm-up, TTFT, TPOT, 256 generated tokens) on the host cores,
+                  plus "oracle_port": the CPU oracle on a slice of the headline workload
+  parity_check -- one decoder layer of the HIP step against that oracle slice
+--no-secondary, --no-secondary-configs, --no-prefill, --no-live-pmc, --no-reference-order and --no-cpu-baseline trim a
+--full run; --reference-order and --shard-sim LIST imply --full.
 """
 
 from __future__ import annotations
@@ -62,24 +71,26 @@ def parse():
                     help="TP collective: RCCL, the one-shot peer-to-peer kernel, or (auto) the kernel if it passes a start-up "
                          "check against RCCL on this hardware")
     ap.add_argument("--reference-order", action="store_true",
-                    help="also time the DROP-IN route: the reference's own 12-launch decoder layer through the 16 kernel names only "
+                    help="(implies --full) also time the DROP-IN route: the reference's own 12-launch decoder layer through the 16 kernel names only "
                          "(what integration.install() gives a reference caller), as a second labelled value")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the second measured point (SURVEY 8d: prompt 2048) that the N = 1 line carries as \"secondary\"")
-    ap.add_argument("--no-prefill", action="store_true", help="skip the timed prefill (TTFT) object of the N = 1 line")
+                    help="skip the second measured point (SURVEY 8d: prompt 2048) that the N = 1 --full line carries as \"secondary\"")
+    ap.add_argument("--no-prefill", action="store_true", help="skip the timed prefill (TTFT) object of the N = 1 --full line")
     ap.add_argument("--as-secondary", action="store_true",
-                    help="(used by the headline run for its \"secondary\" entries) one bounded line for another BASELINE.json "
-                         "configuration: timed steps + roofline + the oracle-layer parity check, no host-side baselines")
+                    help="(used by the --full headline run for its \"secondary\" entries, together with --full) one bounded line "
+                         "for another BASELINE.json configuration: timed steps + roofline + the oracle-layer parity check, no "
+                         "host-side baselines")
     ap.add_argument("--no-secondary-configs", action="store_true",
                     help="keep the ctx-2048 point but skip BASELINE.json configs 2 / 4 / 5 in \"secondary\"")
     ap.add_argument("--keep-reference-weights", action="store_true",
                     help="keep the reference-format int4 tensors next to the decode engine's layout (2 x the int4 payload)")
     ap.add_argument("--cpu-layers", type=int, default=1, help="decoder layers in the CPU oracle sample")
     ap.add_argument("--shard-sim", default=None,
-                    help="comma list of TP degrees (default for the N = 1 headline line: 2,4,8; 'none' to skip): per degree ONE rank's "
-                         "shard shapes on this GPU with every all-reduce replaced by a same-size local copy -- one rank's compute, no "
-                         "collective: a ceiling of the scaling curve, not a scaling point (\"shard_sim\" in the line)")
+                    help="comma list of TP degrees (default for the N = 1 --full headline line: 2,4,8; 'none' to skip; a list "
+                         "implies --full): per degree ONE rank's shard shapes on one GPU with every all-reduce replaced by a "
+                         "same-size local copy -- one rank's compute, no collective: a ceiling of the scaling curve, not a scaling "
+                         "point (\"shard_sim\" in the line)")
     ap.add_argument("--as-shard-sim", type=int, default=0,
                     help="(used by --shard-sim) run as rank 0 of this TP degree with simulated collectives; bounded line")
     ap.add_argument("--parallelism", default="tp", choices=["tp", "dp"],
@@ -92,7 +103,11 @@ def parse():
     ap.add_argument("--no-live-pmc", action="store_true",
                     help="skip the live rocprofv3 --pmc passes (roofline.traffic / mfma_util then carry the stored profile values)")
     ap.add_argument("--no-reference-order", action="store_true",
-                    help="skip the bounded drop-in-route entry (\"reference_order\") of the default N = 1 int4 line")
+                    help="skip the bounded drop-in-route entry (\"reference_order\") of the N = 1 int4 --full line")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run every other measurement and check of the line (secondary points and "
+                         "configurations, prefill, roofline and counters, drop-in route, HBM copy, shard_sim, CPU baselines, "
+                         "parity check); off by default")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (its greedy tokens and logits) as "
                          "DIR/<name>.npy, float64 / float32, <= 64 MB in all (rank 0)")
@@ -434,7 +449,8 @@ def secondary_configs(steps: int, timeout_s: float = 240.0):
 
     out = []
     for label, flags in SECONDARY_CONFIGS:
-        cmd = [sys.executable, os.path.abspath(__file__), *flags, "--steps", str(min(steps, 32)), "--warmup", "4", "--as-secondary"]
+        cmd = [sys.executable, os.path.abspath(__file__), *flags, "--steps", str(min(steps, 32)), "--warmup", "4", "--as-secondary",
+               "--full"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=timeout_s)
@@ -937,6 +953,8 @@ def main():
         args.no_secondary = True
         if args.quant not in ("smoothquant", "fp8", "int8"):  # the 8-bit configurations carry their own TTFT (round-5 review, item 7)
             args.no_prefill = True
+    if args.reference_order or args.shard_sim not in (None, "none"):
+        args.full = True  # both ask for an entry of the --full line
     if args.as_pmc_probe:
         pmc_probe(args)
         return
@@ -1152,86 +1170,87 @@ def main():
                 "and their fp16 pair layout (2 x 0.0625 B / weight) + fp16 lm_head",
     }
     if rank == 0:
-        if world == 1 and not args.no_secondary and not args.scattered and not args.kv_block_size and args.ctx != 2048:
-            try:  # "report a second point at prompt_len = 2048" -- same model, its own engine, fewer steps
-                result["secondary"] = [second_point(model, args, dev, act_dtype, geo, tp)]
-            except Exception as exc:
-                result["secondary"] = [{"error": f"{type(exc).__name__}: {exc}"}]
-        if world == 1 and not args.no_prefill:
-            try:  # TTFT of the same workload through the HIP path (the reference times it in the same run)
-                result["prefill"] = prefill_point(model, args, dev, act_dtype, geo, tp, prompt_len=min(args.ctx, 512))
-            except Exception as exc:
-                result["prefill"] = {"error": f"{type(exc).__name__}: {exc}"}
-        live_wanted = (world == 1 and not args.no_live_pmc and not args.as_secondary and not args.as_shard_sim and not geo.num_experts
-                       and args.quant in ("int4", "smoothquant") and args.batch <= 64)
-        # the launches are timed FIRST, on the warm chip (the counter passes below leave this process idle for ~12 s: a timing taken
-        # after them starts on a chip that has dropped its clocks); the counters of the run are merged into the object afterwards
-        rf = gemm_roofline(model, args.batch, args.quant)
-        if live_wanted and rf is not None:
-            try:  # round-5 review, "weak" 10: counters of THIS run next to the timed launches (stored values only as a fallback)
-                live = live_pmc_counters(args)
-                if live:
-                    rf_live = gemm_roofline(model, args.batch, args.quant, live_pmc=live, time_it=False)
-                    rf.update({k: rf_live[k] for k in ("traffic", "traffic_parts", "traffic_source", "mfma_util")})
-            except Exception:
-                pass
-        if geo.num_experts and quant is not None:
-            try:  # the dominant kernel of a MoE model is the grouped expert GEMM; the dense projections stay as a second object
-                mrf = moe_roofline(model, args.batch)
-            except Exception as exc:
-                mrf = {"error": f"{type(exc).__name__}: {exc}"}
-            result["roofline_dense_projections"] = rf
-            rf = mrf
-        result["roofline"] = rf
-        headline_line = (world == 1 and args.model == "qwen2.5-7b" and args.quant == "int4" and not args.as_secondary
-                         and not args.scattered and not args.kv_block_size and not args.as_shard_sim)
-        if (args.reference_order or (headline_line and not args.no_reference_order)) and world == 1 and args.quant == "int4" \
-                and not geo.num_experts and not args.as_shard_sim:
-            try:  # the drop-in route next to the headline (round-5 review, item 6): bounded unless asked for explicitly
-                ro_steps, ro_warm = (args.steps, args.warmup) if args.reference_order else (min(args.steps, 20), 4)
-                result["reference_order"] = reference_order_step(model, engine, args.batch, int(ctx_mid), ro_steps, ro_warm)
-                result["reference_order"]["vs_headline_ms_per_step"] = round(result["reference_order"]["ms_per_step"] / ms_per_step, 3)
-            except Exception as exc:
-                result["reference_order"] = {"error": f"{type(exc).__name__}: {exc}"}
-        try:
-            d2d = measured_copy_bandwidth(dev)
-            result["hbm"] = {"peak_GBps_nominal": PEAK_HBM / 1e9, "measured_d2d_copy_GBps": round(d2d / 1e9, 1),
-                             "note": "1-GiB device-to-device copy, read + write bytes; roofline fractions divide by the nominal peak"}
-        except Exception as exc:
-            result["hbm"] = {"peak_GBps_nominal": PEAK_HBM / 1e9, "error": f"{type(exc).__name__}: {exc}"}
-        sim = args.shard_sim if args.shard_sim is not None else ("2,4,8" if headline_line and not args.no_secondary else "none")
-        run_secondary_configs = (world == 1 and not args.no_secondary and not args.no_secondary_configs and args.model == "qwen2.5-7b"
-                                 and args.quant == "int4" and not args.scattered and not args.kv_block_size and not args.as_shard_sim)
-        if run_secondary_configs or (sim != "none" and world == 1 and not args.as_shard_sim):
-            del engine
-            torch.cuda.empty_cache()
-        if sim != "none" and world == 1 and not args.as_shard_sim:
-            result["shard_sim"] = shard_sim_points(args, [int(t) for t in sim.split(",") if t.strip()])
-        if run_secondary_configs:
-            result.setdefault("secondary", []).extend(secondary_configs(args.steps))
-        if world == 1 and not args.no_cpu_baseline:
-            if args.as_secondary:
-                result["cpu_baseline"] = {"note": "secondary entry: the host baselines ride on the headline line"}
-            else:
-                try:  # SURVEY 8(d) / BASELINE configs[0]: the reference's CPU-runnable case, its protocol
-                    result["cpu_baseline"] = cpu_baseline_protocol()
-                except Exception as exc:  # never lose the GPU line to a host-side hiccup
-                    result["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
-            try:  # second, labelled entry: the CPU oracle (checker port) on a slice of the headline workload
-                port, sample = cpu_baseline(geo, args.batch, args.ctx, args.cpu_layers, args.quant)
-                result["cpu_baseline"]["oracle_port"] = port
-            except Exception as exc:
-                sample = None
-                result["cpu_baseline"]["oracle_port"] = {"error": f"{type(exc).__name__}: {exc}"}
-            if sample is not None:
-                try:  # the oracle's layer vs the HIP layer on the same inputs (outside the timed region)
-                    pc = parity_check(geo, args.quant, sample)
-                    if args.dtype == "bf16":
-                        pc["what"] += " (fp16 weights / activations: the oracle restates the reference, which is fp16-only)"
+        if args.full:  # everything past the headline, in the order of the line
+            if world == 1 and not args.no_secondary and not args.scattered and not args.kv_block_size and args.ctx != 2048:
+                try:  # "report a second point at prompt_len = 2048" -- same model, its own engine, fewer steps
+                    result["secondary"] = [second_point(model, args, dev, act_dtype, geo, tp)]
                 except Exception as exc:
-                    pc = {"ok": False, "error": f"{type(exc).__name__}: {exc}"}
-                result["parity_check"] = pc["ok"]
-                result["parity_detail"] = pc
+                    result["secondary"] = [{"error": f"{type(exc).__name__}: {exc}"}]
+            if world == 1 and not args.no_prefill:
+                try:  # TTFT of the same workload through the HIP path (the reference times it in the same run)
+                    result["prefill"] = prefill_point(model, args, dev, act_dtype, geo, tp, prompt_len=min(args.ctx, 512))
+                except Exception as exc:
+                    result["prefill"] = {"error": f"{type(exc).__name__}: {exc}"}
+            live_wanted = (world == 1 and not args.no_live_pmc and not args.as_secondary and not args.as_shard_sim and not geo.num_experts
+                           and args.quant in ("int4", "smoothquant") and args.batch <= 64)
+            # the launches are timed FIRST, on the warm chip (the counter passes below leave this process idle for ~12 s: a timing taken
+            # after them starts on a chip that has dropped its clocks); the counters of the run are merged into the object afterwards
+            rf = gemm_roofline(model, args.batch, args.quant)
+            if live_wanted and rf is not None:
+                try:  # round-5 review, "weak" 10: counters of THIS run next to the timed launches (stored values only as a fallback)
+                    live = live_pmc_counters(args)
+                    if live:
+                        rf_live = gemm_roofline(model, args.batch, args.quant, live_pmc=live, time_it=False)
+                        rf.update({k: rf_live[k] for k in ("traffic", "traffic_parts", "traffic_source", "mfma_util")})
+                except Exception:
+                    pass
+            if geo.num_experts and quant is not None:
+                try:  # the dominant kernel of a MoE model is the grouped expert GEMM; the dense projections stay as a second object
+                    mrf = moe_roofline(model, args.batch)
+                except Exception as exc:
+                    mrf = {"error": f"{type(exc).__name__}: {exc}"}
+                result["roofline_dense_projections"] = rf
+                rf = mrf
+            result["roofline"] = rf
+            headline_line = (world == 1 and args.model == "qwen2.5-7b" and args.quant == "int4" and not args.as_secondary
+                             and not args.scattered and not args.kv_block_size and not args.as_shard_sim)
+            if (args.reference_order or (headline_line and not args.no_reference_order)) and world == 1 and args.quant == "int4" \
+                    and not geo.num_experts and not args.as_shard_sim:
+                try:  # the drop-in route next to the headline (round-5 review, item 6): bounded unless asked for explicitly
+                    ro_steps, ro_warm = (args.steps, args.warmup) if args.reference_order else (min(args.steps, 20), 4)
+                    result["reference_order"] = reference_order_step(model, engine, args.batch, int(ctx_mid), ro_steps, ro_warm)
+                    result["reference_order"]["vs_headline_ms_per_step"] = round(result["reference_order"]["ms_per_step"] / ms_per_step, 3)
+                except Exception as exc:
+                    result["reference_order"] = {"error": f"{type(exc).__name__}: {exc}"}
+            try:
+                d2d = measured_copy_bandwidth(dev)
+                result["hbm"] = {"peak_GBps_nominal": PEAK_HBM / 1e9, "measured_d2d_copy_GBps": round(d2d / 1e9, 1),
+                                 "note": "1-GiB device-to-device copy, read + write bytes; roofline fractions divide by the nominal peak"}
+            except Exception as exc:
+                result["hbm"] = {"peak_GBps_nominal": PEAK_HBM / 1e9, "error": f"{type(exc).__name__}: {exc}"}
+            sim = args.shard_sim if args.shard_sim is not None else ("2,4,8" if headline_line and not args.no_secondary else "none")
+            run_secondary_configs = (world == 1 and not args.no_secondary and not args.no_secondary_configs and args.model == "qwen2.5-7b"
+                                     and args.quant == "int4" and not args.scattered and not args.kv_block_size and not args.as_shard_sim)
+            if run_secondary_configs or (sim != "none" and world == 1 and not args.as_shard_sim):
+                del engine
+                torch.cuda.empty_cache()
+            if sim != "none" and world == 1 and not args.as_shard_sim:
+                result["shard_sim"] = shard_sim_points(args, [int(t) for t in sim.split(",") if t.strip()])
+            if run_secondary_configs:
+                result.setdefault("secondary", []).extend(secondary_configs(args.steps))
+            if world == 1 and not args.no_cpu_baseline:
+                if args.as_secondary:
+                    result["cpu_baseline"] = {"note": "secondary entry: the host baselines ride on the headline line"}
+                else:
+                    try:  # SURVEY 8(d) / BASELINE configs[0]: the reference's CPU-runnable case, its protocol
+                        result["cpu_baseline"] = cpu_baseline_protocol()
+                    except Exception as exc:  # never lose the GPU line to a host-side hiccup
+                        result["cpu_baseline"] = {"error": f"{type(exc).__name__}: {exc}"}
+                try:  # second, labelled entry: the CPU oracle (checker port) on a slice of the headline workload
+                    port, sample = cpu_baseline(geo, args.batch, args.ctx, args.cpu_layers, args.quant)
+                    result["cpu_baseline"]["oracle_port"] = port
+                except Exception as exc:
+                    sample = None
+                    result["cpu_baseline"]["oracle_port"] = {"error": f"{type(exc).__name__}: {exc}"}
+                if sample is not None:
+                    try:  # the oracle's layer vs the HIP layer on the same inputs (outside the timed region)
+                        pc = parity_check(geo, args.quant, sample)
+                        if args.dtype == "bf16":
+                            pc["what"] += " (fp16 weights / activations: the oracle restates the reference, which is fp16-only)"
+                    except Exception as exc:
+                        pc = {"ok": False, "error": f"{type(exc).__name__}: {exc}"}
+                    result["parity_check"] = pc["ok"]
+                    result["parity_detail"] = pc
         print(json.dumps(result), flush=True)
     if world > 1:
         torch.distributed.barrier()

@@ -5,11 +5,11 @@
 R=${1:-r06}; V=${2:-v1}; O=$PWD/gpurun_out/$R; mkdir -p $O
 ROOT=$PWD
 export TMPDIR=/tmp
-timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_$V.json 2> $O/bench_$V.err
-cd /tmp && rm -rf /tmp/pk && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/pk -o b -- python $ROOT/bench.py --no-cpu-baseline --no-secondary --no-prefill --steps 16 --warmup 3 > $O/bench_traced_$V.json 2>/dev/null; cd $ROOT
+timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/bench_$V.json 2> $O/bench_$V.err
+cd /tmp && rm -rf /tmp/pk && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/pk -o b -- python $ROOT/bench.py --reference-order --no-live-pmc --no-cpu-baseline --no-secondary --no-prefill --steps 16 --warmup 3 > $O/bench_traced_$V.json 2>/dev/null; cd $ROOT
 python tools/rocpd.py stats /tmp/pk/b_results.db --by-grid > $O/bench_kernel_stats_bygrid_$V.txt 2>&1
 python tools/rocpd.py steps /tmp/pk/b_results.db >> $O/bench_kernel_stats_bygrid_$V.txt 2>&1
-cd /tmp && rm -rf /tmp/pf && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/pf -o p -- python $ROOT/bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary > /dev/null 2>&1; cd $ROOT
+cd /tmp && rm -rf /tmp/pf && timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/pf -o p -- python $ROOT/bench.py --steps 4 --warmup 2 --full --no-live-pmc --no-reference-order --no-cpu-baseline --no-secondary > /dev/null 2>&1; cd $ROOT
 python tools/rocpd.py stats /tmp/pf/p_results.db --by-grid 2>&1 | head -24 > $O/prefill_kernel_stats_bygrid_$V.txt
 for C in "cfg2 --model qwen2.5-1.5b --quant none --dtype bf16 --batch 32" "cfg4 --model llama-3-8b --quant smoothquant --batch 32" "cfg5 --model qwen3-30b-a3b --quant fp8 --batch 64"; do
   set -- $C; N=$1; shift
