@@ -35,6 +35,7 @@ extern "C" {
 #define LL_F16 0
 #define LL_BF16 1
 #define LL_F32 2
+#define LL_FP8E4M3 3 /* KV pool element type only (OCP e4m3 bytes) */
 /* index widths (reference passes int32 or int64 index tensors) */
 #define LL_I32 0
 #define LL_I64 1
@@ -178,6 +179,22 @@ int ll_flash_attention_nopad(void* out, const void* q, const void* k, const void
                              int64_t k_stride_h, int64_t v_stride_t, int64_t v_stride_h,
                              int64_t o_stride_t, int64_t o_stride_h, int dtype, int start_width,
                              int seq_width, void* stream);
+
+/* Causal prefill over the paged KV pool (extension): sequence b has ctx[b] cached tokens and n[b] = b_q_len[b] new
+ * ones, whose queries are rows b_start_loc[b] + j (j < n[b]) of q / out [tokens, hq, d] and whose K / V are already in
+ * the pool.  Query j attends to positions 0 .. ctx[b] + j; position p is pool row table[b_req_idx[b] * table_stride + p]
+ * (k_cache / v_cache: the K and V head views of the [rows, 2 hkv, d] pool).  Softmax as ll_flash_attention_nopad (sm_scale
+ * carries log2 e); rows j >= n[b] are not written; with ctx = 0 and an identity table the two agree.  dtype: F16 / BF16
+ * queries and output; kv_dtype: dtype, or LL_FP8E4M3 with F16 queries and d in {64, 128} (strides in bytes; stored value
+ * * k_scale / v_scale = K / V, as ll_flash_decoding_fp8kv).  16-bit pools: d in {32, 64, 128, 256}.  Caller contract:
+ * n[b] <= max_q_len and ctx[b] + n[b] <= the table row length. */
+int ll_prefill_paged_attention(void* out, const void* q, const void* k_cache, const void* v_cache, const int32_t* table,
+                               const void* b_req_idx, const void* b_start_loc, const void* b_q_len, const void* b_ctx_len,
+                               int batch, int hq, int hkv, int d, int64_t max_q_len, int64_t max_ctx_len, float sm_scale,
+                               float k_scale, float v_scale, int64_t q_stride_t, int64_t q_stride_h, int64_t k_stride_t,
+                               int64_t k_stride_h, int64_t v_stride_t, int64_t v_stride_h, int64_t o_stride_t,
+                               int64_t o_stride_h, int64_t table_stride, int dtype, int kv_dtype, int req_width,
+                               int start_width, int q_len_width, int ctx_width, void* stream);
 
 /* skip_rmsnorm over a projection left as S fp32 split-K partials [S][rows][n] (see ll_w4a16_partials_count):
  * x = fp16(sum_s partials[s]) -- the value the projection would have stored -- then exactly ll_skip_rmsnorm
@@ -496,6 +513,13 @@ int ll_kv_paged_extend(int32_t* free_stack, int32_t* state, int32_t* block_table
                        const int32_t* req_idx, const int32_t* lens, int len_bias, int64_t n, int block_size,
                        int64_t grid_len, int from_end, int32_t* token_table, int64_t tt_stride, int32_t* select_out,
                        int64_t num_blocks, void* stream);
+/* Chunked prefill: request i's grid row holds positions ctx_lens[i] .. ctx_lens[i] + grid_len - 1, the first
+ * chunk_lens[i] of them valid.  Blocks are popped up to ctx_lens[i] + chunk_lens[i] (all-or-nothing per call); valid
+ * positions get token_table[req][p] = row, pads get junk rows in select_out [n * grid_len] and touch no table. */
+int ll_kv_paged_extend_at(int32_t* free_stack, int32_t* state, int32_t* block_table, int64_t bt_stride,
+                          int32_t* req_blocks, const int32_t* req_idx, const int32_t* ctx_lens, const int32_t* chunk_lens,
+                          int64_t n, int block_size, int64_t grid_len, int32_t* token_table, int64_t tt_stride,
+                          int32_t* select_out, int64_t num_blocks, void* stream);
 /* Return every block of the listed requests to the stack (request order, block order). */
 int ll_kv_paged_release(int32_t* free_stack, int32_t* state, const int32_t* block_table, int64_t bt_stride,
                         int32_t* req_blocks, const int32_t* req_idx, int64_t n, void* stream);

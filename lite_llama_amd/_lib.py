@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LL_LIB_OVERRIDE") or os.path.join(_HERE, "lib", "liblite_llama_amd.so")  # override: A/B builds
 
 LL_F16, LL_BF16, LL_F32 = 0, 1, 2
+LL_FP8E4M3 = 3  # KV pool element type only
 LL_I32, LL_I64 = 0, 1
 LL_W_F16, LL_W_FP8E4M3, LL_W_INT8 = 0, 1, 2
 ABI_VERSION = 1
@@ -40,6 +41,8 @@ SIGNATURES = {
     "ll_decode_attention_partials": [P, P, I, P, P, P, L, P, P, I, P, P, P, P, P, I, I, I, I, L, F, L, L, L, L, L, L, L, I, I, I,
                                      P, P, F, P, P, P],
     "ll_flash_attention_nopad": [P, P, P, P, P, P, I, I, I, I, L, F, L, L, L, L, L, L, L, L, I, I, I, P],
+    "ll_prefill_paged_attention": [P, P, P, P, P, P, P, P, P, I, I, I, I, L, L, F, F, F, L, L, L, L, L, L, L, L, L, I, I,
+                                   I, I, I, I, P],
     "ll_gemm_workspace": [L, L, L, P, P],
     "ll_w4a16_matmul": [P, P, P, P, P, P, L, L, L, I, L, L, L, P, P, P],
     "ll_w4a16_pack_scales": [P, P, P, L, L, L, P],
@@ -101,6 +104,7 @@ SIGNATURES = {
     "ll_tp_allreduce_norm_partials": [P, P, I, P, P, L, L, F, I, P, P, I, I, L, I, P, P],
     "ll_kv_paged_reset": [P, P, P, L, L, P],
     "ll_kv_paged_extend": [P, P, P, L, P, P, P, I, L, I, L, I, P, L, P, L, P],
+    "ll_kv_paged_extend_at": [P, P, P, L, P, P, P, P, L, I, L, P, L, P, L, P],
     "ll_kv_paged_release": [P, P, P, L, P, P, L, P],
     "ll_w4_from_awq": [P, P, P, P, P, P, L, L, L, P],
     "ll_w4_from_gptq": [P, P, P, P, P, P, L, L, L, I, P],

@@ -66,7 +66,8 @@ __global__ void paged_reset_kernel(int32_t* free_stack, int32_t* state, int32_t*
 __global__ __launch_bounds__(kMaxBatch) void paged_reserve_kernel(
     const int32_t* __restrict__ free_stack, int32_t* __restrict__ state, int32_t* __restrict__ block_table,
     int64_t bt_stride, int32_t* __restrict__ req_blocks, const int32_t* __restrict__ req_idx,
-    const int32_t* __restrict__ want_len, int len_bias, int n, int block_size, int max_blocks) {
+    const int32_t* __restrict__ want_len, int len_bias, int n, int block_size, int max_blocks,
+    const int32_t* __restrict__ base = nullptr) {
   __shared__ int lds[96];
   const int i = threadIdx.x;
   int req = 0, held = 0, need = 0;
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(kMaxBatch) void paged_reserve_kernel(
   if (i < n) {
     req = req_idx[i];
     held = req_blocks[req];
-    const int len = want_len[i] + len_bias;
+    const int len = want_len[i] + len_bias + (base ? base[i] : 0);
     int want = len > 0 ? (len + block_size - 1) / block_size : 0;
     if (want > max_blocks) {
       want = max_blocks;
@@ -100,19 +101,21 @@ __global__ __launch_bounds__(kMaxBatch) void paged_reserve_kernel(
 // the tables and no request is listed twice in one call.
 // Rows of positions [p_lo, p_hi) of every request on a [n][grid_len] grid: token_table[req][p] = row and
 // select_out[i * grid_len + (p - p_base)] = row; positions the request holds no block for (pads, refused requests)
-// get junk-block rows in select_out and leave the token table alone.
+// get junk-block rows in select_out and leave the token table alone.  base (extend_at): the grid holds positions
+// base[i] .. base[i] + grid_len - 1 of request i, of which the first lens[i] are valid (a chunk that starts at base[i]).
 __global__ void paged_rows_kernel(const int32_t* __restrict__ block_table, int64_t bt_stride,
                                   const int32_t* __restrict__ req_blocks, const int32_t* __restrict__ req_idx,
                                   const int32_t* __restrict__ lens, int len_bias, int n, int block_size, int grid_len,
                                   int from_end, int32_t* __restrict__ token_table, int64_t tt_stride,
-                                  int32_t* __restrict__ select_out, int64_t num_blocks, int32_t* __restrict__ state) {
+                                  int32_t* __restrict__ select_out, int64_t num_blocks, int32_t* __restrict__ state,
+                                  const int32_t* __restrict__ base = nullptr) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)n * grid_len) return;
   const int i = (int)(idx / grid_len), g = (int)(idx - (int64_t)i * grid_len);
   const int req = req_idx[i];
-  const int len = lens[i] + len_bias;
+  const int len = lens[i] + len_bias + (base ? base[i] : 0);
   // from_end: the grid holds the LAST grid_len positions of the request (the decode step: grid_len = 1 -> position len - 1)
-  const int p = from_end ? len - grid_len + g : g;
+  const int p = base ? base[i] + g : from_end ? len - grid_len + g : g;
   const int64_t junk = (num_blocks - 1) * block_size + (p >= 0 ? p % block_size : 0);
   int64_t row = junk;
   if (p >= 0 && p < len && p >= tt_stride) {
@@ -178,6 +181,29 @@ extern "C" int ll_kv_paged_extend(int32_t* free_stack, int32_t* state, int32_t* 
   paged_rows_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(
       block_table, bt_stride, req_blocks, req_idx, lens, len_bias, (int)n, block_size, (int)grid_len, from_end,
       token_table, tt_stride, select_out, num_blocks, state);
+  return LL_LAUNCH_CHECK();
+}
+
+// extend_at: request i's grid holds positions ctx_lens[i] .. ctx_lens[i] + grid_len - 1, of which the first
+// chunk_lens[i] are valid; blocks are popped up to ctx_lens[i] + chunk_lens[i] only and pads get junk rows (a chunked
+// prefill: from_end = 1 with a ragged grid would name the request's own prefix rows for a short chunk's pads).
+extern "C" int ll_kv_paged_extend_at(int32_t* free_stack, int32_t* state, int32_t* block_table, int64_t bt_stride,
+                                     int32_t* req_blocks, const int32_t* req_idx, const int32_t* ctx_lens,
+                                     const int32_t* chunk_lens, int64_t n, int block_size, int64_t grid_len,
+                                     int32_t* token_table, int64_t tt_stride, int32_t* select_out, int64_t num_blocks,
+                                     void* stream) {
+  if (n < 0 || n > kMaxBatch || block_size < 1 || grid_len < 1 || num_blocks < 2 || bt_stride < 1) return LL_ERR_SHAPE;
+  if (n == 0) return LL_OK;
+  if (!free_stack || !state || !block_table || !req_blocks || !req_idx || !ctx_lens || !chunk_lens || !token_table ||
+      !select_out)
+    return LL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  paged_reserve_kernel<<<1, kMaxBatch, 0, st>>>(free_stack, state, block_table, bt_stride, req_blocks, req_idx,
+                                               chunk_lens, 0, (int)n, block_size, (int)bt_stride, ctx_lens);
+  const int64_t total = n * grid_len;
+  paged_rows_kernel<<<dim3((unsigned)((total + 255) / 256)), 256, 0, st>>>(
+      block_table, bt_stride, req_blocks, req_idx, chunk_lens, 0, (int)n, block_size, (int)grid_len, 0, token_table,
+      tt_stride, select_out, num_blocks, state, ctx_lens);
   return LL_LAUNCH_CHECK();
 }
 

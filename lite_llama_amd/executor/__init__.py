@@ -36,6 +36,10 @@ class AttentionMetadata:
     b_req_idx: torch.Tensor | None = None
     b_seq_len: torch.Tensor | None = None
     max_actual_seq_len: int = 0
+    # chunk steps (extension): sequence b already holds b_ctx_len[b] tokens in the pool; b_seq_len / max_actual_seq_len
+    # then count this step's new tokens only (the queries of prefill_paged_attention), max_ctx_len bounds b_ctx_len
+    b_ctx_len: torch.Tensor | None = None
+    max_ctx_len: int = 0
     kv_scales: tuple = (1.0, 1.0)                          # fp8 KV pool only (extension): stored value * scale = K / V
 
 
@@ -121,12 +125,17 @@ class DecodeEngine:
 
     # ------------------------------------------------------------------ prefill ----- #
     @torch.no_grad()
-    def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None) -> torch.Tensor:
+    def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None,
+                chunk_size: int | None = None) -> torch.Tensor:
         """``prompt_ids [B, Lp]`` (right-padded) -> next token per row ``[B]``: greedy, or -- with ``sampling`` -- drawn by
         the same sampler as every later token (llm_engine.py:168-176: the prefill step samples like a decode step; no
-        token has been generated yet, so the repetition penalty has nothing to act on)."""
+        token has been generated yet, so the repetition penalty has nothing to act on).  ``chunk_size`` (extension): run
+        the grid as successive chunk steps ``[B, <= chunk_size]`` (:func:`plan_prefill_chunks`), each attending over
+        what the earlier ones cached; the engine is left as the one-step prefill leaves it."""
         b, lp = prompt_ids.shape
         dev = self.device
+        if chunk_size is not None:
+            return self._first_tokens(self._prefill_chunked(prompt_ids, prompt_lens, int(chunk_size)), sampling)
         self.pool.reset()
         if prompt_lens is None:
             prompt_lens = torch.full((b,), lp, dtype=torch.int32, device=dev)
@@ -151,10 +160,61 @@ class DecodeEngine:
         last = self.model(prompt_ids, position_ids, info, logits_rows=rows)
         self._positions = prompt_lens.long().clone().view(b, 1)
         self._batch = b
+        return self._first_tokens(last, sampling)
+
+    def _first_tokens(self, last: torch.Tensor, sampling) -> torch.Tensor:
         if sampling is None or sampling.temperature == 0.0:
             return greedy_argmax(last)
-        uniform = torch.rand(b, device=dev)
+        uniform = torch.rand(last.shape[0], device=self.device)
         return Sampler().sample(last, sampling, None, uniform=uniform).view(-1)
+
+    def _prefill_chunked(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, chunk_size: int) -> torch.Tensor:
+        """Chunk steps over the prompt grid; returns the logits of every sequence's last prompt token ``[B, vocab]``."""
+        from .chunking import plan_prefill_chunks
+
+        b, lp = prompt_ids.shape
+        dev = self.device
+        self.pool.reset()
+        if prompt_lens is None:
+            prompt_lens = torch.full((b,), lp, dtype=torch.int32, device=dev)
+        plans = plan_prefill_chunks(prompt_lens.tolist(), lp, chunk_size)
+        info = self.info
+        table = info.b_req_tokens_table
+        info.b_req_idx = torch.arange(b, dtype=torch.int32, device=dev)
+        last = None
+        try:
+            for ch in plans:
+                w = ch.width
+                info.b_seq_len = ch.b_q_len.to(dev)
+                info.b_ctx_len = ch.b_ctx_len.to(dev)
+                info.b_start_loc = ch.b_start_loc.to(dev)
+                info.max_actual_seq_len = w
+                info.max_ctx_len = ch.max_ctx_len
+                if self.paged:
+                    # blocks up to ctx + n only; pads write their junk K/V into the junk block
+                    info.cur_select_index = self.pool.extend_at(info.b_req_idx, info.b_ctx_len, info.b_seq_len, w, table)
+                else:
+                    # B * width fresh rows; table[i, ctx_i + j] names them for valid tokens only (pads hold junk K/V)
+                    info.cur_select_index = self.pool.alloc(b * w)
+                    table[ch.valid_rows.to(dev), ch.valid_cols.to(dev)] = info.cur_select_index[ch.valid_flat.to(dev)]
+                # a chunk that ends no sequence still computes one logits row (the lm_head takes no empty batch)
+                rows = ch.logits_rows if ch.ends.numel() else torch.zeros(1, dtype=torch.int64)
+                logits = self.model(prompt_ids[:, ch.col0:ch.col0 + w].contiguous(), ch.positions.to(dev), info,
+                                    logits_rows=rows.to(dev))
+                logits = logits.view(-1, logits.shape[-1])
+                if last is None:
+                    last = torch.empty(b, logits.shape[-1], dtype=logits.dtype, device=dev)
+                if ch.ends.numel():
+                    last[ch.ends.to(dev)] = logits
+        finally:
+            info.b_ctx_len, info.max_ctx_len = None, 0
+        # the state a one-step prefill leaves: decode, graph capture and steps_per_graph run unchanged
+        info.b_seq_len = prompt_lens.to(torch.int32).clone()
+        info.max_actual_seq_len = lp
+        info.b_start_loc = torch.arange(b, dtype=torch.int32, device=dev) * lp
+        self._positions = prompt_lens.long().clone().view(b, 1)
+        self._batch = b
+        return last
 
     @torch.no_grad()
     def synthetic_context(self, batch: int, ctx_len: int, seed: int = 0, scattered: bool = False) -> torch.Tensor:
@@ -386,5 +446,6 @@ class DecodeEngine:
             self.pool.restore(snap[7])
 
 
+from .chunking import ChunkPlan, plan_prefill_chunks  # noqa: E402,F401
 from .slots import DEFAULT_BATCH_SIZES, DEFAULT_SEQ_LEN_BUCKETS, SlotBatch, SlotRunner, StepGraphs, slot_advance  # noqa: E402,F401
 from .kv_cache_manager import KVCacheManager  # noqa: E402,F401

@@ -64,6 +64,31 @@ class PagedKVPool:
         return self._extend(req_idx, seq_len, 0, 1, 1, token_table, out=out)
 
     @torch.no_grad()
+    def extend_at(self, req_idx: torch.Tensor, ctx_lens: torch.Tensor, chunk_lens: torch.Tensor, grid_len: int,
+                  token_table: torch.Tensor, out=None) -> torch.Tensor:
+        """A chunk step: request ``i``'s row of the ``[n, grid_len]`` grid holds positions ``ctx_lens[i] + g``, the first
+        ``chunk_lens[i]`` of them valid.  Blocks are popped up to ``ctx_lens[i] + chunk_lens[i]`` only, valid positions
+        get ``token_table[req, ctx + g]``, pads junk rows (never one of the request's own prefix rows).  Returns / fills
+        ``cur_select_index``."""
+        n = req_idx.numel()
+        L.require_cuda(req_idx, ctx_lens, chunk_lens, token_table)
+        for t in (req_idx, ctx_lens, chunk_lens, token_table):
+            if t.dtype != torch.int32:
+                raise ValueError("PagedKVPool: request indices, lengths and the token table must be int32")
+        if (token_table.stride(1) != 1 or not req_idx.is_contiguous() or not ctx_lens.is_contiguous()
+                or not chunk_lens.is_contiguous() or ctx_lens.numel() != n or chunk_lens.numel() != n):
+            raise ValueError("PagedKVPool: the token table must be row-major, indices and lengths contiguous, one per request")
+        select = out if out is not None else torch.empty(n * grid_len, dtype=torch.int32, device=self.device)
+        if select.dtype != torch.int32 or select.numel() != n * grid_len or not select.is_contiguous():
+            raise ValueError("PagedKVPool: the row output must be a contiguous int32 tensor of n * grid_len entries")
+        L.check(L.lib().ll_kv_paged_extend_at(
+            self.free_stack.data_ptr(), self.state.data_ptr(), self.block_table.data_ptr(), self.block_table.stride(0),
+            self.req_blocks.data_ptr(), req_idx.data_ptr(), ctx_lens.data_ptr(), chunk_lens.data_ptr(), n,
+            self.block_size, grid_len, token_table.data_ptr(), token_table.stride(0), select.data_ptr(), self.num_blocks,
+            L.stream_ptr()), "kv_paged_extend_at")
+        return select
+
+    @torch.no_grad()
     def release(self, req_idx: torch.Tensor) -> None:
         L.require_cuda(req_idx)
         L.check(L.lib().ll_kv_paged_release(self.free_stack.data_ptr(), self.state.data_ptr(), self.block_table.data_ptr(),

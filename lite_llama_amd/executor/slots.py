@@ -143,8 +143,8 @@ class StepGraphs:
         the largest bucket) so the caller runs eager (cuda_graph.py:218-249).  Inputs that already
         live in the persistent vectors are not copied."""
         batch_size, seq_len = input_ids.shape
-        if seq_len != 1 or batch_size not in self.batch_sizes:
-            return None
+        if seq_len != 1 or batch_size not in self.batch_sizes or getattr(atten_info, "b_ctx_len", None) is not None:
+            return None  # (a chunk step one token wide is not a decode step)
         bucket = self._pick_bucket(atten_info.max_actual_seq_len)
         if bucket is None:
             return None
@@ -265,9 +265,18 @@ class SlotBatch:
             r.kv_cache_manager.claim(rows)
 
     # ------------------------------------------------------------------ steps ------- #
-    def begin_prefill(self, slots: Sequence[int], prompt_lens: Sequence[int]) -> None:
+    def begin_prefill(self, slots: Sequence[int], prompt_lens: Sequence[int],
+                      cached_lens: Sequence[int] | None = None) -> None:
         """Sequence ``i``'s token ``j`` of the row-major ``[n, max_prompt_len]`` grid lands in slot
-        ``slots[i]``'s row ``j`` (pad positions write junk the sequence's own decode overwrites)."""
+        ``slots[i]``'s row ``j`` (pad positions write junk the sequence's own decode overwrites).
+
+        ``cached_lens`` (extension: continuing a slot): slot ``slots[i]`` already holds ``cached_lens[i]`` tokens, this
+        step's token ``j`` lands in its row ``cached_lens[i] + j`` and attends over rows ``0 .. cached_lens[i] + j``
+        (feed positions ``cached_lens[i] + j``).  Pad positions then write into the filler slot, never past the slot's
+        own ``max_seq_len`` rows (the next slot's rows follow directly)."""
+        if cached_lens is not None:
+            self._begin_continuation(slots, prompt_lens, cached_lens)
+            return
         longest = max(prompt_lens)
         if longest > self.max_seq_len:
             raise ValueError(f"prompt length {longest} exceeds max_seq_len {self.max_seq_len}")
@@ -277,7 +286,35 @@ class SlotBatch:
         info.b_start_loc = self._row_offsets[: len(slots)] * longest           # packed grid: sequence i starts at i * longest
         info.cur_select_index = info.b_req_tokens_table[rows, :longest].reshape(-1)  # its scatter targets: the row's first columns
         info.max_actual_seq_len = longest
+        info.b_ctx_len = None
         self.reset()  # the next decode step rebuilds its vectors from the host
+
+    def _begin_continuation(self, slots, prompt_lens, cached_lens) -> None:
+        slots, lens, cached = list(slots), [int(v) for v in prompt_lens], [int(v) for v in cached_lens]
+        if not (len(slots) == len(lens) == len(cached)) or not slots:
+            raise ValueError("begin_prefill: slots, prompt_lens and cached_lens must be non-empty and of one length")
+        if min(lens) < 0 or min(cached) < 0:
+            raise ValueError("begin_prefill: lengths must be >= 0")
+        if max(c + n for c, n in zip(cached, lens)) > self.max_seq_len:
+            raise ValueError(f"cached + prompt length exceeds max_seq_len {self.max_seq_len}")
+        longest = max(max(lens), 1)
+        if any(n < longest for n in lens) and self._filler_slot is None:
+            raise ValueError("begin_prefill: a ragged continuation grid needs the filler slot for its pad positions")
+        info = self._atten
+        table = info.b_req_tokens_table
+        rows = self._to_device(slots)
+        n_t, c_t = self._to_device(lens), self._to_device(cached)
+        j = torch.arange(longest, device=self.device)
+        valid = j[None, :] < n_t[:, None]
+        # valid tokens: the slot's own row cached + j; pads: row j of the filler slot (j < longest <= max_seq_len)
+        own = table[rows[:, None], (c_t[:, None] + j[None, :]).clamp(max=table.shape[1] - 1)]
+        pad = table[self._filler_slot if self._filler_slot is not None else slots[0], :longest]
+        info.b_req_idx, info.b_seq_len, info.b_ctx_len = rows, n_t, c_t
+        info.max_ctx_len = max(cached)
+        info.b_start_loc = self._row_offsets[: len(slots)] * longest
+        info.cur_select_index = torch.where(valid, own, pad[None, :]).reshape(-1).contiguous()
+        info.max_actual_seq_len = longest
+        self.reset()
 
     def begin_decode(self, slots: Sequence[int], seq_lens: Sequence[int]) -> int:
         """``seq_lens``: length each sequence has AFTER this step's token (its K/V goes to row
@@ -300,6 +337,7 @@ class SlotBatch:
         self._atten.max_actual_seq_len = max(seq_lens)
         self._atten.cur_select_index = self._cur_select
         self._atten.b_start_loc = None
+        self._atten.b_ctx_len = None
         return len(padded_slots)
 
     def reset(self) -> None:

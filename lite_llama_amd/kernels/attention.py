@@ -277,3 +277,55 @@ def flash_attention2_no_pad(q, k, v, sm_scale, b_start_loc, b_seq_len, max_seq_l
         "flash_attention2_no_pad",
     )
     return output
+
+
+@torch.no_grad()
+def prefill_paged_attention(q, kv_pool, sm_scale, b_req_tokens_table, b_req_idx, b_start_loc, b_q_len, b_ctx_len,
+                            max_q_len, max_ctx_len, kv_scales=(1.0, 1.0), out=None):
+    """Causal prefill attention over the paged KV pool (extension: chunked prefill, continuing a sequence, shared
+    prefixes).  Sequence ``b`` holds ``b_ctx_len[b]`` cached tokens and ``b_q_len[b]`` new ones: their queries are rows
+    ``b_start_loc[b] + j`` (``j < b_q_len[b]``) of ``q [T, Hq, D]`` and their K / V must already be in the pool.  Query
+    ``j`` attends to positions ``0 .. b_ctx_len[b] + j`` inclusive; position ``p`` is pool row
+    ``b_req_tokens_table[b_req_idx[b], p]`` of ``kv_pool [rows, 2*Hkv, D]`` (K heads first, the layout decode reads).
+
+    Softmax as :func:`flash_attention2_no_pad`: ``sm_scale`` must already include log2(e), scores and sums are fp32 and
+    P is rounded to the storage dtype before PV.  With ``b_ctx_len = 0`` and an identity table the result is
+    :func:`flash_attention2_no_pad`'s.  Rows ``j >= b_q_len[b]`` of the output are not written (``out``: an optional
+    preallocated ``[T, Hq, D]`` output).  ``b_q_len[b] = 0`` and ``b_ctx_len[b] = 0`` are both legal; ``max_q_len`` /
+    ``max_ctx_len`` bound them, and ``b_ctx_len[b] + b_q_len[b]`` must fit the table row.
+
+    Pools: fp16 / bf16 (the dtype of ``q``) at head sizes 32, 64, 128, 256, or OCP e4m3 (uint8 / float8_e4m3fn, fp16
+    queries, head sizes 64 and 128) where ``kv_scales = (k_scale, v_scale)`` widen the stored values as in
+    :func:`flash_decoding_fp8kv`.  Index vectors may be int32 or int64; the table is int32.  Anything else raises
+    ``KernelError``: there is no fallback."""
+    L.require_cuda(q, kv_pool, b_req_tokens_table, b_req_idx, b_start_loc, b_q_len, b_ctx_len, out)
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    if b_req_tokens_table.dtype != torch.int32:
+        raise L.KernelError("prefill_paged_attention: the token table must be int32")
+    if b_req_tokens_table.stride(1) != 1:
+        b_req_tokens_table = b_req_tokens_table.contiguous()
+    if kv_pool.stride(-1) != 1 or kv_pool.dim() != 3 or kv_pool.shape[1] % 2 or kv_pool.shape[-1] != q.shape[-1]:
+        raise L.KernelError("prefill_paged_attention: kv_pool must be [rows, 2*Hkv, D] with a contiguous last dim")
+    n_kv = kv_pool.shape[1] // 2
+    fp8 = kv_pool.element_size() == 1
+    kv_code = L.LL_FP8E4M3 if fp8 else L.dtype_code(kv_pool.dtype)
+    if out is None:
+        out = torch.empty_like(q, memory_format=torch.contiguous_format)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
+        raise L.KernelError("prefill_paged_attention: out must match q's shape and dtype")
+    k_cache, v_cache = kv_pool[:, :n_kv], kv_pool[:, n_kv:]
+    ks, vs = (float(s) for s in kv_scales)
+    batchs, n_heads, head_dim = b_q_len.shape[0], q.shape[1], q.shape[2]
+    L.check(
+        L.lib().ll_prefill_paged_attention(
+            out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), b_req_tokens_table.data_ptr(),
+            b_req_idx.data_ptr(), b_start_loc.data_ptr(), b_q_len.data_ptr(), b_ctx_len.data_ptr(), batchs, n_heads,
+            n_kv, head_dim, int(max_q_len), int(max_ctx_len), float(sm_scale), ks, vs, q.stride(0), q.stride(1),
+            k_cache.stride(0), k_cache.stride(1), v_cache.stride(0), v_cache.stride(1), out.stride(0), out.stride(1),
+            b_req_tokens_table.stride(0), L.dtype_code(q.dtype), kv_code, L.index_width(b_req_idx),
+            L.index_width(b_start_loc), L.index_width(b_q_len), L.index_width(b_ctx_len), L.stream_ptr(),
+        ),
+        "prefill_paged_attention",
+    )
+    return out

@@ -35,6 +35,7 @@ from .kernels import (
     update_kv_buffer,
     update_kv_buffer_fp8,
     flash_decoding_fp8kv,
+    prefill_paged_attention,
 )
 from .linear import ColumnParallelLinear, LinearBase, MergedColumnLinear, RowParallelLinear
 from .quantization import QuantConfig, get_moe_method
@@ -204,6 +205,7 @@ class PagedAttention(nn.Module):
         """``xkv [n, 2*Hkv, D]`` = this step's K heads then V heads (the pool's row layout), possibly
         a strided view of the fused projection output; ``cached``: already scattered to the pool."""
         pool = atten_info.kv_buffer[layer_index]
+        chunked = getattr(atten_info, "b_ctx_len", None) is not None  # a step that continues cached sequences
         if pool.element_size() == 1:
             # fp8 KV cache (extension): quantising scatter, then -- decode -- attention over the e4m3 pool; the prefill
             # attention reads the fresh fp16 q / k / v as always
@@ -211,12 +213,16 @@ class PagedAttention(nn.Module):
             if cached:
                 raise ValueError("an fp8 KV pool is written by update_kv_buffer_fp8 only (no fused rope + scatter)")
             update_kv_buffer_fp8(xkv, atten_info.cur_select_index, pool, self.num_kv_heads, ks, vs)
+            if chunked:
+                return self._paged_prefill(xq, pool, atten_info, (ks, vs))
             if not is_prefill:
                 return flash_decoding_fp8kv(xq, pool[:, : self.num_kv_heads, :], pool[:, self.num_kv_heads :, :], self.scale,
                                             atten_info.b_req_tokens_table, atten_info.b_req_idx, atten_info.b_seq_len,
                                             atten_info.max_actual_seq_len, ks, vs)
         elif not cached:
             update_kv_buffer(xkv, atten_info.cur_select_index, atten_info.kv_buffer[layer_index])
+        if chunked:
+            return self._paged_prefill(xq, pool, atten_info)
         if is_prefill:
             xk, xv = xkv[:, : self.num_kv_heads], xkv[:, self.num_kv_heads :]
             return flash_attention2_no_pad(xq, xk, xv, self.scale * _LOG2E, atten_info.b_start_loc,
@@ -225,6 +231,14 @@ class PagedAttention(nn.Module):
         return flash_decoding(xq, kv[:, : self.num_kv_heads, :], kv[:, self.num_kv_heads :, :], self.scale,
                               atten_info.b_req_tokens_table, atten_info.b_req_idx, atten_info.b_seq_len,
                               atten_info.max_actual_seq_len)
+
+
+    def _paged_prefill(self, xq, pool, atten_info, kv_scales=(1.0, 1.0)):
+        """Chunk step (``b_ctx_len`` set, any chunk width, 1 included): the new tokens are in the pool, every query
+        attends over its sequence's cached and new positions through the table."""
+        return prefill_paged_attention(xq, pool, self.scale * _LOG2E, atten_info.b_req_tokens_table, atten_info.b_req_idx,
+                                       atten_info.b_start_loc, atten_info.b_seq_len, atten_info.b_ctx_len,
+                                       atten_info.max_actual_seq_len, atten_info.max_ctx_len, kv_scales)
 
 
 class Attention(nn.Module):
@@ -269,9 +283,10 @@ class Attention(nn.Module):
         # smoothquant q|k|v planes are int32: the attention launch only takes them for head size 128, an fp16 pool and no head
         # norm -- known before the projection runs, so other geometries keep the finished projection (the
         # planes GEMM + a torch finish on every step otherwise, and a bias added after the first rounding)
+        chunked = getattr(atten_info, "b_ctx_len", None) is not None  # chunk step: b_seq_len counts new tokens only
         int32_planes_ok = not getattr(self.q_proj.quant_method, "takes_int8_rows", False) or (
             self.head_dim == 128 and qk_norm is None and atten_info.kv_buffer[layer_index].dtype == torch.float16)
-        if (seq_len == 1 and norm_fused and not _TWO_CALL_ATTENTION and isinstance(position_embeddings, RopeTables)
+        if (seq_len == 1 and not chunked and norm_fused and not _TWO_CALL_ATTENTION and isinstance(position_embeddings, RopeTables)
                 and not fp8_pool and int32_planes_ok and self._qkv.refresh() and not os.environ.get("LL_NO_QKV_PARTIALS")
                 and decode_attention_partials_supported(atten_info.max_actual_seq_len, self.num_heads, self.num_kv_heads,
                                                         self.head_dim, batch=x2.shape[0])):
@@ -309,7 +324,7 @@ class Attention(nn.Module):
         xk, xv = xkv[:, : self.num_kv_heads], xkv[:, self.num_kv_heads :]
         tables = position_embeddings if isinstance(position_embeddings, RopeTables) else None
         dense_rows = xkv.stride(1) == self.head_dim and xq.stride(1) == self.head_dim and not fp8_pool
-        if dense_rows and norm_fused and tables is not None and seq_len == 1 and not _TWO_CALL_ATTENTION:
+        if dense_rows and norm_fused and tables is not None and seq_len == 1 and not chunked and not _TWO_CALL_ATTENTION:
             # decode: (q / k head norm +) rope + KV scatter + attention + partition merge in ONE launch
             out = decode_attention(xq, xkv, tables[0], tables[1], tables[2], atten_info.cur_select_index,
                                    atten_info.kv_buffer[layer_index], self.attn.scale, atten_info.b_req_tokens_table,
