@@ -129,6 +129,28 @@ int ll_flash_decoding(void* out, const void* q, const void* k_cache, const void*
                       int64_t table_stride_b, int dtype, int req_width, int seq_width,
                       int32_t* counters, void* stream);
 
+/* Decode attention for a batch that shares a prompt prefix (extension): ll_flash_decoding's result --
+ * out[b,h,:] = softmax(q[b,h] . K[rows]^T * scale) V[rows], rows = table[b_req_idx[b], :b_seq_len[b]] -- with the K / V rows of
+ * the prefix read once per 64-row tile of the (batch row, head) queries of a KV head instead of once per batch row.
+ * Caller contract: table[b_req_idx[b], p] == table[prefix_req, p] for every p < prefix_len, and b_seq_len[b] >= prefix_len
+ * for every row (a row with b_seq_len[b] == prefix_len gets the prefix-only result).  Prefix positions are read through
+ * table[prefix_req] only; positions prefix_len .. b_seq_len[b] - 1 through the row's own table row.  Three launches (prefix
+ * tiles on MFMA split over the prefix, flash_decoding's stage 1 over the tails, a log-sum-exp merge in fp32 with one
+ * rounding), no host synchronisation and no allocation: capturable.  workspace: ll_shared_prefix_workspace_floats(...) fp32,
+ * 16-byte aligned, no zeroing; ll_shared_prefix_num_splits: the prefix splits of that launch (0: shape not served).
+ * Served: dtype F16 / BF16 (q, out and pool), d in {64, 128}, hq / hkv <= 16, prefix_len >= 64, max_len >= prefix_len
+ * (max_len bounds b_seq_len and sizes the tail partitions from max_len - prefix_len); anything else is LL_ERR_SHAPE and
+ * nothing is written.  K / V views, strides and index widths as for ll_flash_decoding. */
+int ll_shared_prefix_num_splits(int batch, int hq, int hkv, int d, int64_t prefix_len, int64_t max_len);
+int64_t ll_shared_prefix_workspace_floats(int batch, int hq, int hkv, int d, int64_t prefix_len, int64_t max_len);
+int ll_shared_prefix_decode_attention(void* out, const void* q, const void* k_cache, const void* v_cache,
+                                      const int32_t* table, const void* b_req_idx, const void* b_seq_len,
+                                      int64_t prefix_req, int64_t prefix_len, float* workspace, int batch, int hq, int hkv,
+                                      int d, int64_t max_len, float qk_scale, int64_t q_stride_b, int64_t q_stride_h,
+                                      int64_t k_stride_t, int64_t k_stride_h, int64_t v_stride_t, int64_t v_stride_h,
+                                      int64_t o_stride_b, int64_t o_stride_h, int64_t table_stride_b, int dtype,
+                                      int req_width, int seq_width, void* stream);
+
 /* Decode-step attention in one launch (executor extension): rope of q and of the new token's K
  * with position-indexed tables (kernels/rope_emb.py:86-134 arithmetic), the scatter of that K and V
  * into pool row select_index[b] (kernels/update_kv_buffer.py:54-89) and flash_decoding, with the same

@@ -92,6 +92,10 @@ SIGNATURES = {
     "ll_kv_alloc": [P, L, L, I, P, P, P, P, P],
     "ll_kv_ref_update": [P, L, P, L, I, I, P, P],
     "ll_update_kv_buffer_fp8": [P, P, P, L, I, I, I, L, L, L, L, F, F, I, I, P],
+    "ll_shared_prefix_num_splits": [I, I, I, I, L, L],
+    "ll_shared_prefix_workspace_floats": [I, I, I, I, L, L],
+    "ll_shared_prefix_decode_attention": [P, P, P, P, P, P, P, L, L, P, I, I, I, I, L, F, L, L, L, L, L, L, L, L, L, I, I, I,
+                                          P],
     "ll_flash_decoding_fp8kv": [P, P, P, P, P, P, P, P, P, I, I, I, I, L, F, F, F, L, L, L, L, L, L, L, L, L, I, I, P, P],
     "ll_tp_shared_alloc": [P, L],
     "ll_tp_shared_free": [P],
@@ -113,7 +117,8 @@ SIGNATURES = {
     "ll_argmax_split": [P, P, L, L, L, I, P, I, P],
 }
 
-_RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints"}
+_RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints",
+                "ll_shared_prefix_workspace_floats"}
 _lib = None
 
 

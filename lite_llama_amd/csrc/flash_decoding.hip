@@ -14,6 +14,7 @@
 // Numerics follow the reference: fp32 scores/accumulators, plain exp, plain scale.
 #include <stdlib.h>
 
+#include "attn_engines.h"
 #include "common.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -1075,6 +1076,45 @@ static int launch_fd(void* out, const void* q, const void* kc, const void* vc, c
     fd_stage2<DT><<<dim3((unsigned)hq, (unsigned)batch), d, 0, st>>>((uint16_t*)out, mid_o, mid_lse, seq, hq, d,
                                                                      nparts, o_sb, o_sh, seq_w);
   return LL_LAUNCH_CHECK();
+}
+
+// Stage 1 alone for a caller that merges the records itself (attn_engines.h): the launch launch_fd makes without counters.
+template <int DT>
+static int launch_fd_records(const void* q, const void* kc, const void* vc, const int32_t* table, const void* req,
+                             const void* seq, float* mid_o, float* mid_lse, int batch, int hq, int hkv, int d, int64_t max_len,
+                             float scale, int64_t q_sb, int64_t q_sh, int64_t k_st, int64_t k_sh, int64_t v_st, int64_t v_sh,
+                             int64_t t_sb, int req_w, int seq_w, hipStream_t st) {
+  const int nparts = ll_flash_decoding_num_partitions(max_len);
+  const int hgroups = (hq / hkv + 15) / 16;
+  const dim3 grid((unsigned)nparts, (unsigned)(hkv * hgroups), (unsigned)batch);
+#define LL_FDR(DD)                                                                                                       \
+  fd_stage1<DT, DD, false, false, 16, false><<<grid, 64, 32 * (DD + 8) * 2, st>>>(                                       \
+      (const uint16_t*)q, (const uint16_t*)kc, (const uint16_t*)vc, table, req, seq, mid_o, mid_lse, hq, hkv, nparts, scale, \
+      q_sb, q_sh, k_st, k_sh, v_st, v_sh, t_sb, req_w, seq_w, nullptr, 0, 0, nullptr, FdRope{})
+  switch (d) {
+    case 32: LL_FDR(32); break;
+    case 64: LL_FDR(64); break;
+    case 128: LL_FDR(128); break;
+    case 256: LL_FDR(256); break;
+    default: return LL_ERR_SHAPE;
+  }
+#undef LL_FDR
+  return LL_LAUNCH_CHECK();
+}
+
+int fd_stage1_records(const void* q, const void* k_cache, const void* v_cache, const int32_t* table, const void* b_req_idx,
+                      const void* b_seq_len, float* mid_o, float* mid_lse, int batch, int hq, int hkv, int d, int64_t max_len,
+                      float qk_scale, int64_t q_stride_b, int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h,
+                      int64_t v_stride_t, int64_t v_stride_h, int64_t table_stride_b, int dtype, int req_width, int seq_width,
+                      void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == LL_F16)
+    return launch_fd_records<LL_F16>(q, k_cache, v_cache, table, b_req_idx, b_seq_len, mid_o, mid_lse, batch, hq, hkv, d,
+                                     max_len, qk_scale, q_stride_b, q_stride_h, k_stride_t, k_stride_h, v_stride_t,
+                                     v_stride_h, table_stride_b, req_width, seq_width, st);
+  return launch_fd_records<LL_BF16>(q, k_cache, v_cache, table, b_req_idx, b_seq_len, mid_o, mid_lse, batch, hq, hkv, d,
+                                    max_len, qk_scale, q_stride_b, q_stride_h, k_stride_t, k_stride_h, v_stride_t, v_stride_h,
+                                    table_stride_b, req_width, seq_width, st);
 }
 
 static int fd_entry(void* out, const void* q, const void* k_cache, const void* v_cache, const int32_t* table,

@@ -41,6 +41,11 @@ class AttentionMetadata:
     b_ctx_len: torch.Tensor | None = None
     max_ctx_len: int = 0
     kv_scales: tuple = (1.0, 1.0)                          # fp8 KV pool only (extension): stored value * scale = K / V
+    # shared prompt prefix (extension): table[b_req_idx[b], :shared_prefix_len] == table[shared_prefix_req, :shared_prefix_len]
+    # for every row of the batch; 0: no sharing.  Decode steps then read the prefix's K/V once per query tile
+    # (kernels.shared_prefix_decode_attention) from kernels.attention.SHARED_PREFIX_MIN_LEN positions on
+    shared_prefix_len: int = 0
+    shared_prefix_req: int = 0
 
 
 @dataclass
@@ -126,14 +131,19 @@ class DecodeEngine:
     # ------------------------------------------------------------------ prefill ----- #
     @torch.no_grad()
     def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None,
-                chunk_size: int | None = None) -> torch.Tensor:
+                chunk_size: int | None = None, shared_prefix_ids: torch.Tensor | None = None) -> torch.Tensor:
         """``prompt_ids [B, Lp]`` (right-padded) -> next token per row ``[B]``: greedy, or -- with ``sampling`` -- drawn by
         the same sampler as every later token (llm_engine.py:168-176: the prefill step samples like a decode step; no
         token has been generated yet, so the repetition penalty has nothing to act on).  ``chunk_size`` (extension): run
         the grid as successive chunk steps ``[B, <= chunk_size]`` (:func:`plan_prefill_chunks`), each attending over
-        what the earlier ones cached; the engine is left as the one-step prefill leaves it."""
+        what the earlier ones cached; the engine is left as the one-step prefill leaves it.  ``shared_prefix_ids`` (extension,
+        int64 ``[P]``): every row's prompt is these tokens followed by its row of ``prompt_ids`` (its own tail, at least one
+        token) -- the prefix is prefilled and cached once, see :meth:`_prefill_shared`."""
         b, lp = prompt_ids.shape
         dev = self.device
+        self.info.shared_prefix_len, self.info.shared_prefix_req = 0, 0
+        if shared_prefix_ids is not None:
+            return self._first_tokens(self._prefill_shared(shared_prefix_ids, prompt_ids, prompt_lens, chunk_size), sampling)
         if chunk_size is not None:
             return self._first_tokens(self._prefill_chunked(prompt_ids, prompt_lens, int(chunk_size)), sampling)
         self.pool.reset()
@@ -168,13 +178,67 @@ class DecodeEngine:
         uniform = torch.rand(last.shape[0], device=self.device)
         return Sampler().sample(last, sampling, None, uniform=uniform).view(-1)
 
-    def _prefill_chunked(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, chunk_size: int) -> torch.Tensor:
-        """Chunk steps over the prompt grid; returns the logits of every sequence's last prompt token ``[B, vocab]``."""
+    def _prefill_shared(self, prefix_ids: torch.Tensor, tail_ids: torch.Tensor, tail_lens: torch.Tensor | None,
+                        chunk_size: int | None) -> torch.Tensor:
+        """One prompt prefix for the whole batch: the prefix is prefilled once, as one sequence, into ``P`` fresh pool rows
+        named by table row 0; rows ``1 .. B-1`` of the table get the same ``P`` entries; the tails run as chunk steps with
+        ``b_ctx_len = P`` (positions ``P + j``), attending over the shared rows through their own table rows.  The pool
+        then holds ``P + B x tail grid`` rows instead of ``B x (P + ...)``, and the engine is in the state a one-step
+        prefill of the concatenated prompts leaves, with ``info.shared_prefix_len = P``.  Returns the logits of every
+        sequence's last prompt token ``[B, vocab]``."""
+        if self.paged:
+            raise ValueError("shared_prefix_ids needs the bump pool: sharing blocks of a paged pool (kv_block_size) would "
+                             "need per-block reference counts")
+        dev = self.device
+        b, lt = tail_ids.shape
+        prefix_ids = prefix_ids.reshape(-1).to(dev)
+        p = prefix_ids.numel()
+        if p < 1:
+            raise ValueError("shared_prefix_ids is empty")
+        if tail_lens is None:
+            tail_lens = torch.full((b,), lt, dtype=torch.int32, device=dev)
+        lens = [int(v) for v in tail_lens.tolist()]
+        if lt < 1 or min(lens) < 1:
+            raise ValueError("every row needs a tail of at least one token after the shared prefix")
+        if p + max(lens) > self.max_seq_len:
+            raise ValueError(f"prefix {p} + tail {max(lens)} exceeds max_seq_len {self.max_seq_len}")
+        info = self.info
+        table = info.b_req_tokens_table
+        self.pool.reset()
+        # 1. the prefix as one sequence (table row 0); its logits are not needed beyond one row for the lm_head
+        info.b_req_idx = torch.zeros(1, dtype=torch.int32, device=dev)
+        info.b_seq_len = torch.full((1,), p, dtype=torch.int32, device=dev)
+        info.max_actual_seq_len = p
+        info.b_start_loc = torch.zeros(1, dtype=torch.int32, device=dev)
+        info.cur_select_index = self.pool.alloc(p)
+        table[0, :p] = info.cur_select_index
+        self.model(prefix_ids.view(1, p), torch.arange(p, device=dev).view(1, p), info,
+                   logits_rows=torch.tensor([p - 1], device=dev))
+        # 2. every row names the same P pool rows
+        if b > 1:
+            table[1:b, :p] = table[0, :p]
+        # 3. the tails, as chunk steps on top of the cached prefix
+        last = self._prefill_chunked(tail_ids, tail_lens, lt if chunk_size is None else int(chunk_size), ctx0=p)
+        # 4. the state a one-step prefill of the concatenated prompts leaves
+        total = tail_lens.to(device=dev, dtype=torch.int32) + p
+        info.b_seq_len = total.clone()
+        info.max_actual_seq_len = p + lt
+        info.b_start_loc = torch.arange(b, dtype=torch.int32, device=dev) * (p + lt)
+        self._positions = total.long().view(b, 1)
+        info.shared_prefix_len, info.shared_prefix_req = p, 0
+        return last
+
+    def _prefill_chunked(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, chunk_size: int,
+                         ctx0: int = 0) -> torch.Tensor:
+        """Chunk steps over the prompt grid; returns the logits of every sequence's last prompt token ``[B, vocab]``.
+        ``ctx0``: every sequence already holds that many cached positions (a shared prefix the table rows name); the pool is
+        then left as it is and the grid's column ``j`` is position ``ctx0 + j``."""
         from .chunking import plan_prefill_chunks
 
         b, lp = prompt_ids.shape
         dev = self.device
-        self.pool.reset()
+        if ctx0 == 0:
+            self.pool.reset()
         if prompt_lens is None:
             prompt_lens = torch.full((b,), lp, dtype=torch.int32, device=dev)
         plans = plan_prefill_chunks(prompt_lens.tolist(), lp, chunk_size)
@@ -186,20 +250,20 @@ class DecodeEngine:
             for ch in plans:
                 w = ch.width
                 info.b_seq_len = ch.b_q_len.to(dev)
-                info.b_ctx_len = ch.b_ctx_len.to(dev)
+                info.b_ctx_len = ch.b_ctx_len.to(dev) + ctx0
                 info.b_start_loc = ch.b_start_loc.to(dev)
                 info.max_actual_seq_len = w
-                info.max_ctx_len = ch.max_ctx_len
+                info.max_ctx_len = ch.max_ctx_len + ctx0
                 if self.paged:
                     # blocks up to ctx + n only; pads write their junk K/V into the junk block
                     info.cur_select_index = self.pool.extend_at(info.b_req_idx, info.b_ctx_len, info.b_seq_len, w, table)
                 else:
                     # B * width fresh rows; table[i, ctx_i + j] names them for valid tokens only (pads hold junk K/V)
                     info.cur_select_index = self.pool.alloc(b * w)
-                    table[ch.valid_rows.to(dev), ch.valid_cols.to(dev)] = info.cur_select_index[ch.valid_flat.to(dev)]
+                    table[ch.valid_rows.to(dev), ch.valid_cols.to(dev) + ctx0] = info.cur_select_index[ch.valid_flat.to(dev)]
                 # a chunk that ends no sequence still computes one logits row (the lm_head takes no empty batch)
                 rows = ch.logits_rows if ch.ends.numel() else torch.zeros(1, dtype=torch.int64)
-                logits = self.model(prompt_ids[:, ch.col0:ch.col0 + w].contiguous(), ch.positions.to(dev), info,
+                logits = self.model(prompt_ids[:, ch.col0:ch.col0 + w].contiguous(), ch.positions.to(dev) + ctx0, info,
                                     logits_rows=rows.to(dev))
                 logits = logits.view(-1, logits.shape[-1])
                 if last is None:
@@ -226,6 +290,7 @@ class DecodeEngine:
         dev = self.device
         self.pool.reset()
         info = self.info
+        info.shared_prefix_len, info.shared_prefix_req = 0, 0
         g = torch.Generator(device=dev)
         g.manual_seed(seed)
         info.b_req_idx = torch.arange(batch, dtype=torch.int32, device=dev)

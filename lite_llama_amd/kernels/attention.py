@@ -86,6 +86,101 @@ def flash_decoding(
     return out
 
 
+# Routing threshold of the shared-prefix decode route (tokens): from this prefix length on, ``PagedAttention`` answers a
+# decode step whose metadata names a shared prefix with ``shared_prefix_decode_attention`` (rope + KV scatter, then the
+# three launches) instead of the one-launch decode attention.  Measured, DESIGN 4.7.
+SHARED_PREFIX_MIN_LEN = 2048
+
+# fp32 workspace of the shared-prefix launches, cached like the merge counters: per (device, stream) for eager calls, per
+# device for captures; outgrown buffers stay alive for graphs that captured their address.
+_sp_workspace: dict = {}
+
+
+def _grow_sp_workspace(key, device, floats: int):
+    cur = _sp_workspace.get(key)
+    if cur is not None and cur.numel() >= floats:
+        return cur
+    if torch.cuda.is_current_stream_capturing():
+        return torch.empty(floats, dtype=torch.float32, device=device)  # the capture's own pool keeps it alive
+    if cur is not None:
+        _fd_keepalive.append(cur)
+    cur = torch.empty(floats, dtype=torch.float32, device=device)
+    _sp_workspace[key] = cur
+    return cur
+
+
+def _shared_prefix_workspace(device, floats: int):
+    key, cap = L.scratch_keys(device)
+    if key != cap:
+        _grow_sp_workspace(cap, device, floats)
+    return _grow_sp_workspace(key, device, floats)
+
+
+def shared_prefix_supported(q_dtype, kv_dtype, num_heads: int, num_kv_heads: int, head_dim: int, prefix_len: int,
+                            max_len: int) -> bool:
+    """Shapes :func:`shared_prefix_decode_attention` serves (host integers and dtypes only)."""
+    return (q_dtype in (torch.float16, torch.bfloat16) and kv_dtype == q_dtype and head_dim in (64, 128)
+            and num_kv_heads > 0 and num_heads % num_kv_heads == 0 and 1 <= num_heads // num_kv_heads <= 16
+            and int(prefix_len) >= 64 and int(max_len) >= int(prefix_len))
+
+
+@torch.no_grad()
+def shared_prefix_decode_attention(q, k_cache, v_cache, qk_scale, b_req_tokens_table, b_req_idx, b_seq_len,
+                                   max_actual_seq_len, prefix_len: int, prefix_req: int = 0, out=None):
+    """:func:`flash_decoding` for a batch whose sequences share their first ``prefix_len`` positions (extension): the
+    caller promises ``b_req_tokens_table[b_req_idx[b], :prefix_len] == b_req_tokens_table[prefix_req, :prefix_len]`` and
+    ``b_seq_len[b] >= prefix_len`` for every row.  The prefix's K / V rows are then read once per 64-row tile of the
+    batch's queries (an MFMA GEMM per KV head, split over the prefix), every row's own tail goes through
+    ``flash_decoding``'s stage 1, and one fp32 log-sum-exp merge writes the result -- the values of ``flash_decoding`` up
+    to summation order.  Nothing on the host reads the device-side lengths: the launches are capturable.
+
+    Returns ``None`` (nothing launched, ``out`` untouched) when the shape is not served -- an e4m3 pool, a head size other
+    than 64 / 128, more than 16 query heads per KV head, ``prefix_len < 64`` or ``max_actual_seq_len < prefix_len`` -- so
+    the caller takes the ordinary route, which reads an aliased table correctly as it is."""
+    if q.dim() != 3 or k_cache.dim() != 3 or v_cache.dim() != 3:
+        raise ValueError("shared_prefix_decode_attention: q [B, Hq, D], k_cache / v_cache [rows, Hkv, D]")
+    if b_req_tokens_table.dtype != torch.int32:
+        raise ValueError("shared_prefix_decode_attention: the token table must be int32")
+    batchs, num_heads, head_dim = q.shape
+    n_kv = k_cache.shape[1]
+    prefix_len, prefix_req, max_len = int(prefix_len), int(prefix_req), int(max_actual_seq_len)
+    if k_cache.shape != v_cache.shape or k_cache.shape[-1] != head_dim or k_cache.dtype != v_cache.dtype:
+        raise ValueError("shared_prefix_decode_attention: k_cache and v_cache must be views of one pool with q's head size")
+    if b_req_idx.shape[0] != batchs or b_seq_len.shape[0] != batchs:
+        raise ValueError("shared_prefix_decode_attention: b_req_idx / b_seq_len must hold one entry per row of q")
+    if not 0 <= prefix_req < b_req_tokens_table.shape[0]:
+        raise ValueError(f"shared_prefix_decode_attention: prefix_req {prefix_req} is not a row of the token table")
+    if prefix_len > b_req_tokens_table.shape[1]:
+        raise ValueError(f"shared_prefix_decode_attention: prefix_len {prefix_len} exceeds the table row")
+    if n_kv == 0 or num_heads % n_kv:
+        raise ValueError("shared_prefix_decode_attention: the query heads must be a multiple of the KV heads")
+    L.require_cuda(q, k_cache, v_cache, b_req_tokens_table, b_req_idx, b_seq_len, out)
+    if not shared_prefix_supported(q.dtype, k_cache.dtype, num_heads, n_kv, head_dim, prefix_len, max_len):
+        return None
+    if q.stride(-1) != 1:
+        q = q.contiguous()
+    assert k_cache.stride(-1) == 1 and v_cache.stride(-1) == 1
+    if b_req_tokens_table.stride(1) != 1:
+        b_req_tokens_table = b_req_tokens_table.contiguous()
+    if out is None:
+        out = torch.empty_like(q, memory_format=torch.contiguous_format)
+    elif out.shape != q.shape or out.dtype != q.dtype or out.stride(-1) != 1:
+        raise ValueError("shared_prefix_decode_attention: out must match q's shape and dtype")
+    if batchs == 0:
+        return out
+    floats = L.lib().ll_shared_prefix_workspace_floats(batchs, num_heads, n_kv, head_dim, prefix_len, max_len)
+    ws = _shared_prefix_workspace(q.device, int(floats))
+    rc = L.lib().ll_shared_prefix_decode_attention(
+        out.data_ptr(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), b_req_tokens_table.data_ptr(),
+        b_req_idx.data_ptr(), b_seq_len.data_ptr(), prefix_req, prefix_len, ws.data_ptr(), batchs, num_heads, n_kv,
+        head_dim, max_len, float(qk_scale), q.stride(0), q.stride(1), k_cache.stride(0), k_cache.stride(1),
+        v_cache.stride(0), v_cache.stride(1), out.stride(0), out.stride(1), b_req_tokens_table.stride(0),
+        L.dtype_code(q.dtype), L.index_width(b_req_idx), L.index_width(b_seq_len), L.stream_ptr(),
+    )
+    L.check(rc, "shared_prefix_decode_attention")
+    return out
+
+
 @torch.no_grad()
 def flash_decoding_fp8kv(q, k_cache, v_cache, qk_scale, b_req_tokens_table, b_req_idx, b_seq_len, max_actual_seq_len,
                          k_scale: float = 1.0, v_scale: float = 1.0):

@@ -24,7 +24,9 @@ import torch.nn.functional as F
 
 from .distributed.parallel_state import all_reduce_tp, divide, get_tp_rank, get_tp_world_size
 from .distributed.partition import ShardPlan, make_plan, scale_unit, set_active_plan
-from .kernels.attention import decode_attention, decode_attention_partials, decode_attention_partials_supported
+from .kernels import attention as _attention_kernels
+from .kernels.attention import (decode_attention, decode_attention_partials, decode_attention_partials_supported,
+                                shared_prefix_decode_attention, shared_prefix_supported)
 from .kernels.norm_act import Int8Rows, PartialSums, ScaledInt32Partials, rope_and_cache, skip_rmsnorm_partials, skip_rmsnorm_q8
 from .kernels import (
     flash_attention2_no_pad,
@@ -191,6 +193,16 @@ _TWO_CALL_ATTENTION = os.environ.get("LL_TWO_CALL_ATTENTION", "0") == "1"
 _Q8_FUSION = os.environ.get("LL_NO_Q8_FUSION", "0") != "1"  # smoothquant: quantiser inside the norm launch (A/B knob)
 
 
+def shared_prefix_route(atten_info, is_prefill: bool) -> bool:
+    """Whether this step's attention takes the shared-prefix decode route: a decode step (not a chunk step) whose metadata
+    names a shared prefix of at least ``SHARED_PREFIX_MIN_LEN`` positions (the measured routing threshold, read at call
+    time; never below the kernel's one 64-key tile)."""
+    plen = int(getattr(atten_info, "shared_prefix_len", 0) or 0)
+    if plen <= 0 or is_prefill or getattr(atten_info, "b_ctx_len", None) is not None:
+        return False
+    return plen >= max(_attention_kernels.SHARED_PREFIX_MIN_LEN, 64) and int(atten_info.max_actual_seq_len) >= plen
+
+
 class PagedAttention(nn.Module):
     """KV scatter + phase kernel over the token-attention pool ``[max_tokens, 2*Hkv, D]``
     (K heads first, then V heads) -- base.py:50-142."""
@@ -228,6 +240,15 @@ class PagedAttention(nn.Module):
             return flash_attention2_no_pad(xq, xk, xv, self.scale * _LOG2E, atten_info.b_start_loc,
                                            atten_info.b_seq_len, atten_info.max_actual_seq_len)
         kv = atten_info.kv_buffer[layer_index]
+        if shared_prefix_route(atten_info, is_prefill):
+            # the batch shares its first positions (same pool rows in every table row): their K/V are read once per query
+            # tile; None = shape not served, the ordinary route reads the aliased table as it is
+            out = shared_prefix_decode_attention(xq, kv[:, : self.num_kv_heads, :], kv[:, self.num_kv_heads :, :], self.scale,
+                                                 atten_info.b_req_tokens_table, atten_info.b_req_idx, atten_info.b_seq_len,
+                                                 atten_info.max_actual_seq_len, atten_info.shared_prefix_len,
+                                                 atten_info.shared_prefix_req)
+            if out is not None:
+                return out
         return flash_decoding(xq, kv[:, : self.num_kv_heads, :], kv[:, self.num_kv_heads :, :], self.scale,
                               atten_info.b_req_tokens_table, atten_info.b_req_idx, atten_info.b_seq_len,
                               atten_info.max_actual_seq_len)
@@ -284,9 +305,14 @@ class Attention(nn.Module):
         # norm -- known before the projection runs, so other geometries keep the finished projection (the
         # planes GEMM + a torch finish on every step otherwise, and a bias added after the first rounding)
         chunked = getattr(atten_info, "b_ctx_len", None) is not None  # chunk step: b_seq_len counts new tokens only
+        # a decode step over a shared prompt prefix: rope + KV scatter, then PagedAttention's shared-prefix route
+        two_call = _TWO_CALL_ATTENTION or (
+            seq_len == 1 and shared_prefix_route(atten_info, False)
+            and shared_prefix_supported(x.dtype, atten_info.kv_buffer[layer_index].dtype, self.num_heads, self.num_kv_heads,
+                                        self.head_dim, atten_info.shared_prefix_len, atten_info.max_actual_seq_len))
         int32_planes_ok = not getattr(self.q_proj.quant_method, "takes_int8_rows", False) or (
             self.head_dim == 128 and qk_norm is None and atten_info.kv_buffer[layer_index].dtype == torch.float16)
-        if (seq_len == 1 and not chunked and norm_fused and not _TWO_CALL_ATTENTION and isinstance(position_embeddings, RopeTables)
+        if (seq_len == 1 and not chunked and norm_fused and not two_call and isinstance(position_embeddings, RopeTables)
                 and not fp8_pool and int32_planes_ok and self._qkv.refresh() and not os.environ.get("LL_NO_QKV_PARTIALS")
                 and decode_attention_partials_supported(atten_info.max_actual_seq_len, self.num_heads, self.num_kv_heads,
                                                         self.head_dim, batch=x2.shape[0])):
@@ -324,7 +350,7 @@ class Attention(nn.Module):
         xk, xv = xkv[:, : self.num_kv_heads], xkv[:, self.num_kv_heads :]
         tables = position_embeddings if isinstance(position_embeddings, RopeTables) else None
         dense_rows = xkv.stride(1) == self.head_dim and xq.stride(1) == self.head_dim and not fp8_pool
-        if dense_rows and norm_fused and tables is not None and seq_len == 1 and not chunked and not _TWO_CALL_ATTENTION:
+        if dense_rows and norm_fused and tables is not None and seq_len == 1 and not chunked and not two_call:
             # decode: (q / k head norm +) rope + KV scatter + attention + partition merge in ONE launch
             out = decode_attention(xq, xkv, tables[0], tables[1], tables[2], atten_info.cur_select_index,
                                    atten_info.kv_buffer[layer_index], self.attn.scale, atten_info.b_req_tokens_table,
