@@ -545,6 +545,29 @@ int ll_kv_paged_extend_at(int32_t* free_stack, int32_t* state, int32_t* block_ta
 /* Return every block of the listed requests to the stack (request order, block order). */
 int ll_kv_paged_release(int32_t* free_stack, int32_t* state, const int32_t* block_table, int64_t bt_stride,
                         int32_t* req_blocks, const int32_t* req_idx, int64_t n, void* stream);
+/* Shared blocks (opt-in; a pool that never forks needs neither entry).  block_share [num_blocks] = holders of a block
+ * minus one (0 for a free block and for a block with one holder; the owner zeroes it with the pool).  share_scratch
+ * [2 * num_blocks + 2], zero at rest.  Error flag 4 = a fork that breaks its contract.
+ * Fork i (call order): request dst_req[i] names the first lens[i] / block_size blocks of src_req[i] (share count + 1
+ * each) and, if lens[i] % block_size, gets the next block off the stack with rows [0, lens[i] % block_size) of the
+ * source's block copied into it in every layer (layer_base: device array of num_layers pool base pointers; row_bytes:
+ * bytes of one pool row, a multiple of 16); token_table[dst][p] is filled for p < lens[i].  Shared blocks are never
+ * written afterwards: every writer writes at or beyond its own length.  All-or-nothing per call: flag 4 if a dst holds
+ * a block, is listed twice or is a source of the same call, or a length is < 1 or reaches beyond the source's blocks or
+ * the token-table row; flag 1 if the stack is short; then no table, no count and no pool row changes.  The same source may be listed many times and a dst may be a source
+ * of a LATER call.  Request indices inside the tables are the caller's contract, as for the entries above.  Two
+ * stream-ordered launches. */
+int ll_kv_paged_fork(const int32_t* free_stack, int32_t* state, int32_t* block_table, int64_t bt_stride,
+                     int32_t* req_blocks, int32_t* block_share, int32_t* share_scratch, const int32_t* src_req,
+                     const int32_t* dst_req, const int32_t* lens, int64_t n, int block_size, int32_t* token_table,
+                     int64_t tt_stride, void* const* layer_base, int64_t num_layers, int64_t row_bytes,
+                     int64_t num_blocks, void* stream);
+/* ll_kv_paged_release with share counts: in request order, block order, a block whose count is > 0 loses one holder
+ * and a block whose count is 0 goes back on the stack -- also when several holders of a block are listed in one call
+ * (the last of them in call order pushes it, at its place).  With all counts zero: exactly ll_kv_paged_release. */
+int ll_kv_paged_release_shared(int32_t* free_stack, int32_t* state, const int32_t* block_table, int64_t bt_stride,
+                               int32_t* req_blocks, int32_t* block_share, int32_t* share_scratch, const int32_t* req_idx,
+                               int64_t n, int64_t num_blocks, void* stream);
 
 /* ---- load-time ingestion of third-party int4 checkpoint layouts -------------
  * The reference reaches W4A16 only by re-quantising fp16 weights: AutoAWQ / AutoGPTQ tensors map

@@ -110,6 +110,8 @@ SIGNATURES = {
     "ll_kv_paged_extend": [P, P, P, L, P, P, P, I, L, I, L, I, P, L, P, L, P],
     "ll_kv_paged_extend_at": [P, P, P, L, P, P, P, P, L, I, L, P, L, P, L, P],
     "ll_kv_paged_release": [P, P, P, L, P, P, L, P],
+    "ll_kv_paged_fork": [P, P, P, L, P, P, P, P, P, P, L, I, P, L, P, L, L, L, P],
+    "ll_kv_paged_release_shared": [P, P, P, L, P, P, P, P, L, L, P],
     "ll_w4_from_awq": [P, P, P, P, P, P, L, L, L, P],
     "ll_w4_from_gptq": [P, P, P, P, P, P, L, L, L, I, P],
     "ll_repetition_penalty": [P, P, P, P, P, F, L, L, L, L, L, L, L, I, I, P],

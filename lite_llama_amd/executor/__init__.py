@@ -101,10 +101,14 @@ class DecodeEngine:
     """
 
     def __init__(self, model, max_batch: int, max_seq_len: int, device="cuda", kv_dtype=torch.float16,
-                 kv_block_size: int | None = None, kv_scales: tuple = (1.0, 1.0)):
+                 kv_block_size: int | None = None, kv_scales: tuple = (1.0, 1.0), kv_share_blocks: bool = False):
         """``kv_block_size`` (extension): hand the KV pool out in blocks of that many rows from a device-side
         free stack (:class:`PagedKVPool`) instead of the reference's bump allocator; the kernels read the same per-token
-        table either way, so the generated tokens are identical."""
+        table either way, so the generated tokens are identical.  ``kv_share_blocks`` (with ``kv_block_size``): the pool
+        keeps a share count per block, so requests can name the same full blocks -- ``prefill(shared_prefix_ids=...)`` and
+        ``prefill(num_samples=...)`` on the paged pool."""
+        if kv_share_blocks and kv_block_size is None:
+            raise ValueError("kv_share_blocks needs kv_block_size: share counts are kept per block of the paged pool")
         geo = model.geo
         self.model = model
         self.device = device
@@ -112,12 +116,13 @@ class DecodeEngine:
         self.max_seq_len = max_seq_len
         at0 = model.layers[0].self_attn
         self.paged = kv_block_size is not None
+        self.share_blocks = bool(kv_share_blocks)
         if self.paged:
             from .paged_kv import PagedKVPool
 
             per_req = (max_seq_len + kv_block_size - 1) // kv_block_size
             self.pool = PagedKVPool(geo.num_layers, max_batch * per_req + 1, kv_block_size, at0.num_kv_heads, geo.head_dim,
-                                    device, max_batch, max_seq_len, kv_dtype)
+                                    device, max_batch, max_seq_len, kv_dtype, share_blocks=self.share_blocks)
         else:
             self.pool = KVPool(geo.num_layers, max_batch * max_seq_len, at0.num_kv_heads, geo.head_dim, device, kv_dtype)
         self.info = AttentionMetadata(kv_buffer=self.pool.kv_buffer, kv_scales=tuple(float(v) for v in kv_scales))
@@ -131,26 +136,49 @@ class DecodeEngine:
     # ------------------------------------------------------------------ prefill ----- #
     @torch.no_grad()
     def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None,
-                chunk_size: int | None = None, shared_prefix_ids: torch.Tensor | None = None) -> torch.Tensor:
+                chunk_size: int | None = None, shared_prefix_ids: torch.Tensor | None = None,
+                num_samples: int | None = None) -> torch.Tensor:
         """``prompt_ids [B, Lp]`` (right-padded) -> next token per row ``[B]``: greedy, or -- with ``sampling`` -- drawn by
         the same sampler as every later token (llm_engine.py:168-176: the prefill step samples like a decode step; no
         token has been generated yet, so the repetition penalty has nothing to act on).  ``chunk_size`` (extension): run
         the grid as successive chunk steps ``[B, <= chunk_size]`` (:func:`plan_prefill_chunks`), each attending over
         what the earlier ones cached; the engine is left as the one-step prefill leaves it.  ``shared_prefix_ids`` (extension,
         int64 ``[P]``): every row's prompt is these tokens followed by its row of ``prompt_ids`` (its own tail, at least one
-        token) -- the prefix is prefilled and cached once, see :meth:`_prefill_shared`."""
-        b, lp = prompt_ids.shape
-        dev = self.device
+        token) -- the prefix is prefilled and cached once, see :meth:`_prefill_shared`.  ``num_samples`` (extension, needs
+        ``kv_share_blocks``): ``n`` continuations of every prompt -- ``[B * n]`` tokens, row ``i * n + s`` = sample ``s`` of
+        prompt ``i``; every prompt is prefilled and cached once, see :meth:`_prefill_samples`."""
+        b = prompt_ids.shape[0]
+        if num_samples is not None:
+            if shared_prefix_ids is not None:
+                raise ValueError("num_samples cannot be combined with shared_prefix_ids: the decode route serves one shared "
+                                 "prefix per batch, not one per prompt on top of a common one")
+            if not self.share_blocks:
+                raise ValueError("num_samples needs kv_share_blocks (and kv_block_size): the samples of a prompt name the "
+                                 "prompt's KV blocks, which takes per-block share counts")
+            if int(num_samples) < 1 or b * int(num_samples) > self.max_batch:
+                raise ValueError(f"num_samples {num_samples} x {b} prompts must give between 1 and max_batch "
+                                 f"{self.max_batch} rows")
         self.info.shared_prefix_len, self.info.shared_prefix_req = 0, 0
+        if num_samples is not None:
+            return self._prefill_samples(prompt_ids, prompt_lens, sampling, chunk_size, int(num_samples))
         if shared_prefix_ids is not None:
             return self._first_tokens(self._prefill_shared(shared_prefix_ids, prompt_ids, prompt_lens, chunk_size), sampling)
         if chunk_size is not None:
             return self._first_tokens(self._prefill_chunked(prompt_ids, prompt_lens, int(chunk_size)), sampling)
+        return self._first_tokens(self._prefill_one_step(prompt_ids, prompt_lens), sampling)
+
+    def _prefill_one_step(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, req_stride: int = 1) -> torch.Tensor:
+        """The whole padded grid in one step; returns the logits of every sequence's last prompt token ``[B, vocab]``.
+        ``req_stride``: prompt ``i`` is request ``i * req_stride`` (room for its samples; paged pool only)."""
+        b, lp = prompt_ids.shape
+        dev = self.device
         self.pool.reset()
         if prompt_lens is None:
             prompt_lens = torch.full((b,), lp, dtype=torch.int32, device=dev)
         info = self.info
         info.b_req_idx = torch.arange(b, dtype=torch.int32, device=dev)
+        if req_stride != 1:
+            info.b_req_idx = info.b_req_idx * req_stride
         info.b_seq_len = prompt_lens.to(torch.int32).clone()
         info.max_actual_seq_len = lp
         info.b_start_loc = torch.arange(b, dtype=torch.int32, device=dev) * lp
@@ -170,7 +198,40 @@ class DecodeEngine:
         last = self.model(prompt_ids, position_ids, info, logits_rows=rows)
         self._positions = prompt_lens.long().clone().view(b, 1)
         self._batch = b
-        return self._first_tokens(last, sampling)
+        return last
+
+    def _prefill_samples(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, sampling, chunk_size: int | None,
+                         n: int) -> torch.Tensor:
+        """``n`` samples per prompt on the shared paged pool: prompt ``i`` is prefilled once, as request ``i * n``; requests
+        ``i * n + 1 .. i * n + n - 1`` are forked from it (they name its full blocks and get a copy of the partial last
+        one); the last-token logits are repeated per sample and every row draws its own first token.  The engine is left in
+        the state a one-step prefill of the prompts each repeated ``n`` times leaves.  One prompt with several samples: they
+        share ``(len // block_size) * block_size`` positions, which the decode steps read once (``info.shared_prefix_len``;
+        several prompts are several prefixes, which the decode route does not serve: 0 then, as with ``n = 1``, where
+        nothing is shared and the engine does exactly what it does without ``num_samples``)."""
+        b, lp = prompt_ids.shape
+        dev = self.device
+        if chunk_size is not None:
+            last = self._prefill_chunked(prompt_ids, prompt_lens, int(chunk_size), req_stride=n)
+        else:
+            last = self._prefill_one_step(prompt_ids, prompt_lens, req_stride=n)
+        info = self.info
+        lens = info.b_seq_len                                   # int32 [B], the prompts' lengths
+        if n > 1:
+            rows = torch.arange(b * n, dtype=torch.int32, device=dev)
+            parents = info.b_req_idx.repeat_interleave(n - 1).contiguous()
+            children = rows[rows % n != 0].contiguous()
+            self.pool.fork(parents, children, lens.repeat_interleave(n - 1).contiguous(), info.b_req_tokens_table)
+        info.b_req_idx = torch.arange(b * n, dtype=torch.int32, device=dev)
+        info.b_seq_len = lens.repeat_interleave(n).contiguous()
+        info.b_start_loc = torch.arange(b * n, dtype=torch.int32, device=dev) * lp
+        info.max_actual_seq_len = lp
+        self._positions = info.b_seq_len.long().view(b * n, 1)
+        self._batch = b * n
+        if b == 1 and n > 1:
+            bs = self.pool.block_size
+            info.shared_prefix_len, info.shared_prefix_req = (int(lens[0]) // bs) * bs, 0
+        return self._first_tokens(last.repeat_interleave(n, dim=0), sampling)
 
     def _first_tokens(self, last: torch.Tensor, sampling) -> torch.Tensor:
         if sampling is None or sampling.temperature == 0.0:
@@ -185,8 +246,13 @@ class DecodeEngine:
         ``b_ctx_len = P`` (positions ``P + j``), attending over the shared rows through their own table rows.  The pool
         then holds ``P + B x tail grid`` rows instead of ``B x (P + ...)``, and the engine is in the state a one-step
         prefill of the concatenated prompts leaves, with ``info.shared_prefix_len = P``.  Returns the logits of every
-        sequence's last prompt token ``[B, vocab]``."""
-        if self.paged:
+        sequence's last prompt token ``[B, vocab]``.
+
+        On the paged pool (``kv_share_blocks``) request 0 is admitted with the ``P`` prefix tokens and requests ``1 .. B-1``
+        are forked from it: they name its ``P // block_size`` full blocks and get a private copy of the partial last one,
+        so the rows agree over ``(P // block_size) * block_size`` positions only -- that is ``info.shared_prefix_len``
+        then -- and no shared block is written by the tails or the decode steps (they write at positions >= ``P``)."""
+        if self.paged and not self.share_blocks:
             raise ValueError("shared_prefix_ids needs the bump pool: sharing blocks of a paged pool (kv_block_size) would "
                              "need per-block reference counts")
         dev = self.device
@@ -210,12 +276,19 @@ class DecodeEngine:
         info.b_seq_len = torch.full((1,), p, dtype=torch.int32, device=dev)
         info.max_actual_seq_len = p
         info.b_start_loc = torch.zeros(1, dtype=torch.int32, device=dev)
-        info.cur_select_index = self.pool.alloc(p)
-        table[0, :p] = info.cur_select_index
+        if self.paged:
+            info.cur_select_index = self.pool.admit(info.b_req_idx, info.b_seq_len, p, table)
+        else:
+            info.cur_select_index = self.pool.alloc(p)
+            table[0, :p] = info.cur_select_index
         self.model(prefix_ids.view(1, p), torch.arange(p, device=dev).view(1, p), info,
                    logits_rows=torch.tensor([p - 1], device=dev))
         # 2. every row names the same P pool rows
-        if b > 1:
+        if b > 1 and self.paged:
+            self.pool.fork(torch.zeros(b - 1, dtype=torch.int32, device=dev),
+                           torch.arange(1, b, dtype=torch.int32, device=dev),
+                           torch.full((b - 1,), p, dtype=torch.int32, device=dev), table)
+        elif b > 1:
             table[1:b, :p] = table[0, :p]
         # 3. the tails, as chunk steps on top of the cached prefix
         last = self._prefill_chunked(tail_ids, tail_lens, lt if chunk_size is None else int(chunk_size), ctx0=p)
@@ -226,13 +299,16 @@ class DecodeEngine:
         info.b_start_loc = torch.arange(b, dtype=torch.int32, device=dev) * (p + lt)
         self._positions = total.long().view(b, 1)
         info.shared_prefix_len, info.shared_prefix_req = p, 0
+        if self.paged:
+            info.shared_prefix_len = p // self.pool.block_size * self.pool.block_size
         return last
 
     def _prefill_chunked(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, chunk_size: int,
-                         ctx0: int = 0) -> torch.Tensor:
+                         ctx0: int = 0, req_stride: int = 1) -> torch.Tensor:
         """Chunk steps over the prompt grid; returns the logits of every sequence's last prompt token ``[B, vocab]``.
         ``ctx0``: every sequence already holds that many cached positions (a shared prefix the table rows name); the pool is
-        then left as it is and the grid's column ``j`` is position ``ctx0 + j``."""
+        then left as it is and the grid's column ``j`` is position ``ctx0 + j``.  ``req_stride``: as in
+        :meth:`_prefill_one_step`."""
         from .chunking import plan_prefill_chunks
 
         b, lp = prompt_ids.shape
@@ -245,6 +321,8 @@ class DecodeEngine:
         info = self.info
         table = info.b_req_tokens_table
         info.b_req_idx = torch.arange(b, dtype=torch.int32, device=dev)
+        if req_stride != 1:
+            info.b_req_idx = info.b_req_idx * req_stride
         last = None
         try:
             for ch in plans:
@@ -490,7 +568,8 @@ class DecodeEngine:
             err = self.pool.error
             if err:
                 raise RuntimeError(f"paged KV pool reported error bits {err:#x} (1: a call found too few free blocks, "
-                                   "2: a request outgrew its block-table / token-table row)")
+                                   "2: a request outgrew its block-table / token-table row, 4: a fork "
+                                   "broke its contract)")
 
     def _snapshot(self):
         info = self.info
