@@ -622,6 +622,26 @@ int ll_sample_top_p(int64_t* out, const void* logits, const float* temperature, 
                     const float* uniform, const void* greedy, int64_t batch, int64_t vocab,
                     int64_t stride, int dtype, void* stream);
 
+/* ---- token log-probabilities (the third kernel of the sampler row) -------------------------
+ * Per row of logits [rows, vocab] (F16 / BF16 / F32, row stride in elements, unit column stride), with
+ * lse = max + ln(sum exp(z - max)) accumulated in fp32 and col = *column (0 when column is NULL):
+ *   chosen[row * chosen_stride + col]                      = z[token_ids[row]] - lse   (token_ids int64 [rows], NULL with
+ *       chosen NULL to skip; an id outside [0, vocab) gives NaN and reads nothing);
+ *   top_logprobs[row * top_logprobs_stride + col * top_k + j], top_ids[row * top_ids_stride + col * top_k + j], j < top_k:
+ *       the top_k (0 .. 20, <= vocab) largest logits of the row minus lse and their indices, ordered by (logit descending,
+ *       index ascending) on the stored values -- top_ids[.., 0] is what ll_argmax returns.
+ * column is read on the device (an engine passes its step counter: one captured launch fills successive columns of
+ * [rows, T] / [rows, T, top_k] buffers on successive replays); a column outside [0, num_columns) writes nothing.  Finite
+ * logits are the contract.  The row is read once; no allocation, no host synchronisation.  scratch: at least
+ * ll_token_logprobs_scratch_bytes(rows, vocab, top_k) bytes, 4-byte aligned, written by every call (host-side query, no
+ * device needed: LL_ERR_SHAPE for rows <= 0 or vocab outside 1 .. 2^30, LL_ERR_ARG for top_k outside 0 .. min(20, vocab)). */
+int64_t ll_token_logprobs_scratch_bytes(int64_t rows, int64_t vocab, int top_k);
+int ll_token_logprobs(float* chosen, float* top_logprobs, int64_t* top_ids, const void* logits,
+                      const int64_t* token_ids, const int64_t* column, int64_t rows, int64_t vocab,
+                      int64_t logits_stride, int top_k, int64_t num_columns, int64_t chosen_stride,
+                      int64_t top_logprobs_stride, int64_t top_ids_stride, int dtype, void* scratch,
+                      int64_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,9 @@ this module raises, loudly.  Build it with ``python -m lite_llama_amd.build``.
 
 from __future__ import annotations
 
+import contextlib
 import ctypes
+import gc
 import os
 from ctypes import c_float, c_int, c_int64, c_void_p
 
@@ -117,10 +119,12 @@ SIGNATURES = {
     "ll_repetition_penalty": [P, P, P, P, P, F, L, L, L, L, L, L, L, I, I, P],
     "ll_sample_top_p": [P, P, P, P, P, P, L, L, L, I, P],
     "ll_argmax_split": [P, P, L, L, L, I, P, I, P],
+    "ll_token_logprobs_scratch_bytes": [L, L, I],
+    "ll_token_logprobs": [P, P, P, P, P, P, L, L, L, I, L, L, L, L, I, P, L, P],
 }
 
 _RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints",
-                "ll_shared_prefix_workspace_floats"}
+                "ll_shared_prefix_workspace_floats", "ll_token_logprobs_scratch_bytes"}
 _lib = None
 
 
@@ -147,6 +151,23 @@ def lib() -> ctypes.CDLL:
             raise RuntimeError("lite_llama_amd: ABI version mismatch between _lib.py and the .so")
         _lib = handle
     return _lib
+
+
+@contextlib.contextmanager
+def graph_capture(graph):
+    """``torch.cuda.graph(graph)`` with Python's garbage collector held off until the capture has ended.  A collection pass
+    that falls into a capture finalises whatever GPU objects dead reference cycles still hold (graphs and pools of engines
+    long gone, tensors inside the frames of a caught exception) through runtime calls that are not allowed while a stream
+    captures -- the process aborts.  (``torch.cuda.graph`` used to collect on entry and no longer does; collecting here
+    would also move what the allocator hands the capture.)  The garbage is collected by a later pass, outside the capture."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 def stream_ptr() -> int:

@@ -22,7 +22,7 @@ import torch
 
 from .. import _lib as L
 from ..kernels import update_kv_index
-from ..sampling import Sampler, greedy_argmax
+from ..sampling import MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, greedy_argmax, token_logprobs
 
 
 @dataclass
@@ -54,6 +54,22 @@ class _Span:
 
     token_ids: torch.Tensor
     mask: torch.Tensor
+
+
+# DecodeEngine.score: the lm_head runs over this many bytes of logits at a time (the [B x L x vocab] matrix is never formed)
+SCORE_LOGITS_BYTES = 256 << 20
+# ... in lm_head calls of exactly this many rows each (the last one padded): whatever kernel serves that shape serves every
+# row, so a row's logits do not depend on how many rows are scored or on how they are grouped into chunks
+SCORE_GEMM_ROWS = 256
+
+
+def _check_logprobs(logprobs) -> int | None:
+    if logprobs is None:
+        return None
+    k = int(logprobs)
+    if not 0 <= k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"logprobs must be None or the number of alternatives to report, 0 .. {MAX_TOP_LOGPROBS}; got {logprobs}")
+    return k
 
 
 class KVPool:
@@ -130,6 +146,12 @@ class DecodeEngine:
         self._graph = None
         self._graph_key = None
         self._sampling = None
+        # log-probabilities (extension): of the token prefill returned / of every token of the last decode, when asked for
+        self.first_logprobs: TokenLogprobs | None = None
+        self.last_logprobs: TokenLogprobs | None = None
+        self._prefill_logprobs = None
+        self._logprobs_k = None
+        self._lp = None
         if hasattr(model, "rotary_emb") and torch.device(device).type == "cuda":
             model.rotary_emb.ensure(max_seq_len + 1, device, model.embed_tokens.weight.dtype)
 
@@ -137,7 +159,7 @@ class DecodeEngine:
     @torch.no_grad()
     def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None,
                 chunk_size: int | None = None, shared_prefix_ids: torch.Tensor | None = None,
-                num_samples: int | None = None) -> torch.Tensor:
+                num_samples: int | None = None, logprobs: int | None = None) -> torch.Tensor:
         """``prompt_ids [B, Lp]`` (right-padded) -> next token per row ``[B]``: greedy, or -- with ``sampling`` -- drawn by
         the same sampler as every later token (llm_engine.py:168-176: the prefill step samples like a decode step; no
         token has been generated yet, so the repetition penalty has nothing to act on).  ``chunk_size`` (extension): run
@@ -146,8 +168,13 @@ class DecodeEngine:
         int64 ``[P]``): every row's prompt is these tokens followed by its row of ``prompt_ids`` (its own tail, at least one
         token) -- the prefix is prefilled and cached once, see :meth:`_prefill_shared`.  ``num_samples`` (extension, needs
         ``kv_share_blocks``): ``n`` continuations of every prompt -- ``[B * n]`` tokens, row ``i * n + s`` = sample ``s`` of
-        prompt ``i``; every prompt is prefilled and cached once, see :meth:`_prefill_samples`."""
+        prompt ``i``; every prompt is prefilled and cached once, see :meth:`_prefill_samples`.  ``logprobs`` (extension, an
+        integer ``k >= 0``): ``self.first_logprobs`` is left holding the log-probability of every returned token and the
+        ``k`` most likely alternatives (``T = 1``), under the model's own distribution -- the log-softmax of the raw logits,
+        before temperature and nucleus filter; on every route, since all of them end in :meth:`_first_tokens`."""
         b = prompt_ids.shape[0]
+        self._prefill_logprobs = _check_logprobs(logprobs)
+        self.first_logprobs = None
         if num_samples is not None:
             if shared_prefix_ids is not None:
                 raise ValueError("num_samples cannot be combined with shared_prefix_ids: the decode route serves one shared "
@@ -167,9 +194,12 @@ class DecodeEngine:
             return self._first_tokens(self._prefill_chunked(prompt_ids, prompt_lens, int(chunk_size)), sampling)
         return self._first_tokens(self._prefill_one_step(prompt_ids, prompt_lens), sampling)
 
-    def _prefill_one_step(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, req_stride: int = 1) -> torch.Tensor:
+    def _prefill_one_step(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, req_stride: int = 1,
+                          collect=None) -> torch.Tensor:
         """The whole padded grid in one step; returns the logits of every sequence's last prompt token ``[B, vocab]``.
-        ``req_stride``: prompt ``i`` is request ``i * req_stride`` (room for its samples; paged pool only)."""
+        ``req_stride``: prompt ``i`` is request ``i * req_stride`` (room for its samples; paged pool only).  ``collect``
+        (:meth:`score`): called with ``(first column, final hidden states [B, width, hidden])`` in place of the lm_head;
+        nothing is returned then."""
         b, lp = prompt_ids.shape
         dev = self.device
         self.pool.reset()
@@ -194,8 +224,12 @@ class DecodeEngine:
             info.b_req_tokens_table[:b, :lp] = torch.where(valid, info.cur_select_index.view(b, lp),
                                                            info.b_req_tokens_table[:b, :lp])
         position_ids = torch.arange(lp, device=dev).unsqueeze(0).expand(b, lp)
-        rows = torch.arange(b, device=dev) * lp + (prompt_lens.long() - 1)
-        last = self.model(prompt_ids, position_ids, info, logits_rows=rows)
+        if collect is not None:
+            collect(0, self.model.final_hidden_states(prompt_ids, position_ids, info))
+            last = None
+        else:
+            rows = torch.arange(b, device=dev) * lp + (prompt_lens.long() - 1)
+            last = self.model(prompt_ids, position_ids, info, logits_rows=rows)
         self._positions = prompt_lens.long().clone().view(b, 1)
         self._batch = b
         return last
@@ -235,9 +269,13 @@ class DecodeEngine:
 
     def _first_tokens(self, last: torch.Tensor, sampling) -> torch.Tensor:
         if sampling is None or sampling.temperature == 0.0:
-            return greedy_argmax(last)
-        uniform = torch.rand(last.shape[0], device=self.device)
-        return Sampler().sample(last, sampling, None, uniform=uniform).view(-1)
+            tokens = greedy_argmax(last)
+        else:
+            uniform = torch.rand(last.shape[0], device=self.device)
+            tokens = Sampler().sample(last, sampling, None, uniform=uniform).view(-1)
+        if self._prefill_logprobs is not None:
+            self.first_logprobs = token_logprobs(last, tokens, self._prefill_logprobs)
+        return tokens
 
     def _prefill_shared(self, prefix_ids: torch.Tensor, tail_ids: torch.Tensor, tail_lens: torch.Tensor | None,
                         chunk_size: int | None) -> torch.Tensor:
@@ -304,11 +342,11 @@ class DecodeEngine:
         return last
 
     def _prefill_chunked(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None, chunk_size: int,
-                         ctx0: int = 0, req_stride: int = 1) -> torch.Tensor:
+                         ctx0: int = 0, req_stride: int = 1, collect=None) -> torch.Tensor:
         """Chunk steps over the prompt grid; returns the logits of every sequence's last prompt token ``[B, vocab]``.
         ``ctx0``: every sequence already holds that many cached positions (a shared prefix the table rows name); the pool is
         then left as it is and the grid's column ``j`` is position ``ctx0 + j``.  ``req_stride``: as in
-        :meth:`_prefill_one_step`."""
+        :meth:`_prefill_one_step`; so is ``collect``."""
         from .chunking import plan_prefill_chunks
 
         b, lp = prompt_ids.shape
@@ -339,6 +377,10 @@ class DecodeEngine:
                     # B * width fresh rows; table[i, ctx_i + j] names them for valid tokens only (pads hold junk K/V)
                     info.cur_select_index = self.pool.alloc(b * w)
                     table[ch.valid_rows.to(dev), ch.valid_cols.to(dev) + ctx0] = info.cur_select_index[ch.valid_flat.to(dev)]
+                if collect is not None:
+                    collect(ch.col0, self.model.final_hidden_states(prompt_ids[:, ch.col0:ch.col0 + w].contiguous(),
+                                                                    ch.positions.to(dev) + ctx0, info))
+                    continue
                 # a chunk that ends no sequence still computes one logits row (the lm_head takes no empty batch)
                 rows = ch.logits_rows if ch.ends.numel() else torch.zeros(1, dtype=torch.int64)
                 logits = self.model(prompt_ids[:, ch.col0:ch.col0 + w].contiguous(), ch.positions.to(dev) + ctx0, info,
@@ -357,6 +399,68 @@ class DecodeEngine:
         self._positions = prompt_lens.long().clone().view(b, 1)
         self._batch = b
         return last
+
+    # ------------------------------------------------------------------ score ------- #
+    @torch.no_grad()
+    def score(self, token_ids: torch.Tensor, lens: torch.Tensor | None = None, chunk_size: int | None = None,
+              top_k: int = 0, logits_rows: int | None = None) -> TokenLogprobs:
+        """Log-likelihood of given text (extension): ``token_ids [B, L]`` (right-padded to ``lens``) -> :class:`TokenLogprobs`
+        with ``T = L - 1``, entry ``[i, j] = log P(token_ids[i, j + 1] | token_ids[i, :j + 1])`` for ``j + 1 < lens[i]`` and
+        ``0.0`` (``top_ids = -1``) on padding: ``cumulative()`` is the sequence log-likelihood, ``-cumulative() / (lens - 1)``
+        the per-token negative log-likelihood.  Runs the prefill path (either pool, optionally in chunk steps), then the
+        lm_head and the log-probability kernel over the final hidden states ``logits_rows`` rows at a time (rounded down to
+        whole lm_head calls of ``SCORE_GEMM_ROWS`` rows; default: ``SCORE_LOGITS_BYTES`` of logits), so the logits stay a
+        bounded temporary.  The pool is used as a prefill uses it: call :meth:`prefill` again before :meth:`decode`."""
+        k = _check_logprobs(top_k)
+        dev = self.device
+        b, l = token_ids.shape
+        token_ids = token_ids.to(dev)
+        lens_t = torch.full((b,), l, dtype=torch.int32, device=dev) if lens is None else lens.to(device=dev, dtype=torch.int32)
+        if b > self.max_batch or l > self.max_seq_len:
+            raise ValueError(f"token_ids {b} x {l} exceeds max_batch {self.max_batch} x max_seq_len {self.max_seq_len}")
+        out = TokenLogprobs(torch.zeros(b, max(l - 1, 0), dtype=torch.float32, device=dev),
+                            torch.zeros(b, max(l - 1, 0), k, dtype=torch.float32, device=dev),
+                            torch.full((b, max(l - 1, 0), k), -1, dtype=torch.int64, device=dev))
+        if l < 2:
+            return out
+        self.info.shared_prefix_len, self.info.shared_prefix_req = 0, 0
+        hidden = torch.empty(b, l, self.model.geo.hidden_size, dtype=self.model.norm_weight.dtype, device=dev)
+
+        def collect(col0, h):
+            hidden[:, col0:col0 + h.shape[1]] = h.view(b, -1, hidden.shape[-1])
+
+        if chunk_size is not None:
+            self._prefill_chunked(token_ids, lens_t, int(chunk_size), collect=collect)
+        else:
+            self._prefill_one_step(token_ids, lens_t, collect=collect)
+        # position (i, j) predicts token (i, j + 1): the rows with j + 1 < lens[i]
+        valid = torch.arange(1, l, device=dev).unsqueeze(0) < lens_t.view(b, 1)
+        src = valid.nonzero()                                   # [n, 2], row-major
+        n = src.shape[0]
+        flat = src[:, 0] * l + src[:, 1]
+        targets = token_ids.reshape(-1)[flat + 1].to(torch.int64).contiguous()
+        vocab = self.model.lm_head_weight.shape[0]
+        g = SCORE_GEMM_ROWS
+        step = int(logits_rows) if logits_rows is not None else SCORE_LOGITS_BYTES // (2 * vocab)
+        step = max(g, min(step, 4096) // g * g)
+        got = TokenLogprobs(torch.empty(n, 1, dtype=torch.float32, device=dev),
+                            torch.empty(n, 1, k, dtype=torch.float32, device=dev),
+                            torch.empty(n, 1, k, dtype=torch.int64, device=dev))
+        hidden = hidden.view(b * l, -1)
+        rows_in = torch.zeros(min(step, (n + g - 1) // g * g), hidden.shape[-1], dtype=hidden.dtype, device=dev)
+        logits = torch.empty(rows_in.shape[0], vocab, dtype=hidden.dtype, device=dev)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            rows_in[:r1 - r0] = hidden[flat[r0:r1]]
+            for g0 in range(0, r1 - r0, g):
+                logits[g0:g0 + g] = self.model.logits_from_hidden(rows_in[g0:g0 + g])
+            token_logprobs(logits[:r1 - r0], targets[r0:r1], k,
+                           out=TokenLogprobs(got.chosen[r0:r1], got.top_logprobs[r0:r1], got.top_ids[r0:r1]))
+        out.chosen[src[:, 0], src[:, 1]] = got.chosen[:, 0]
+        if k:
+            out.top_logprobs[src[:, 0], src[:, 1]] = got.top_logprobs[:, 0]
+            out.top_ids[src[:, 0], src[:, 1]] = got.top_ids[:, 0]
+        return out
 
     @torch.no_grad()
     def synthetic_context(self, batch: int, ctx_len: int, seed: int = 0, scattered: bool = False) -> torch.Tensor:
@@ -415,12 +519,22 @@ class DecodeEngine:
         self._out[:, 0] = first_tokens.view(b)
         self._step = torch.ones(1, dtype=torch.long, device=dev)
         self._row_base = torch.arange(b, device=dev) * (max_new_tokens + 1)
+        # log-probability buffers laid out like _out (column 0 = the prefill's token, not filled here), so the kernel
+        # writes at column _step as it stands
+        k = self._logprobs_k
+        self._lp = None if k is None else TokenLogprobs(
+            torch.zeros(b, max_new_tokens + 1, dtype=torch.float32, device=dev),
+            torch.zeros(b, max_new_tokens + 1, k, dtype=torch.float32, device=dev),
+            torch.full((b, max_new_tokens + 1, k), -1, dtype=torch.int64, device=dev))
 
     def _step_body(self):
         """forward -> greedy sample -> record -> advance metadata (all on device)."""
         info, b = self.info, self._batch
-        logits = self.model(self._input_ids, self._positions, info)
-        nxt = self._sample(logits[:, -1, :])
+        logits = self.model(self._input_ids, self._positions, info)[:, -1, :]
+        nxt = self._sample(logits)
+        if self._lp is not None:
+            # the model's own distribution: the raw logits (_sample penalises a copy); before _advance moves _step on
+            token_logprobs(logits, nxt, self._logprobs_k, out=self._lp, column=self._step)
         self._advance(nxt)
 
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
@@ -474,7 +588,8 @@ class DecodeEngine:
 
     @torch.no_grad()
     def decode(self, first_tokens: torch.Tensor, max_new_tokens: int, use_graph: bool = True,
-               warmup_steps: int = 0, on_step=None, sampling=None, steps_per_graph: int = 1) -> torch.Tensor:
+               warmup_steps: int = 0, on_step=None, sampling=None, steps_per_graph: int = 1,
+               logprobs: int | None = None) -> torch.Tensor:
         """Generate ``max_new_tokens`` greedy tokens per row; returns ``[B, max_new_tokens]``.
 
         With ``use_graph`` the step is captured once (``max_actual_seq_len`` baked as the final
@@ -484,7 +599,14 @@ class DecodeEngine:
         engine/llm_engine.py:137-213): that many consecutive steps are captured in ONE hipGraph -- every step already
         advances its own metadata on the device, so the steps chain without the host -- and a remainder shorter than the
         group replays a one-step graph; ``on_step(i)`` then fires once per replay with the index of its first step.
+        ``logprobs`` (extension; ``None``: the step holds exactly the launches it holds without it): an integer ``k >= 0``
+        makes every step record, inside the step (captured with it), the log-probability of the token it emitted and the
+        ``k`` most likely alternatives under the model's own distribution (log-softmax of the raw logits: before repetition
+        penalty, temperature and nucleus filter); ``self.last_logprobs`` then holds them, column ``t`` describing returned
+        token ``[:, t]``.  The returned tokens are the same either way.
         """
+        self._logprobs_k = _check_logprobs(logprobs)
+        self.last_logprobs = None
         self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty
         self._begin_decode(first_tokens, max_new_tokens)
         info = self.info
@@ -511,7 +633,7 @@ class DecodeEngine:
             self._check_device_errors()
             graph = torch.cuda.CUDAGraph()
             try:
-                with torch.cuda.graph(graph):
+                with L.graph_capture(graph):
                     self._step_body()
             except Exception:
                 # a refused capture (e.g. a collective the backend cannot record) must not leave the stream in capture
@@ -529,7 +651,7 @@ class DecodeEngine:
             multi = None
             if group > 1:
                 multi = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(multi):
+                with L.graph_capture(multi):
                     for _ in range(group):
                         self._step_body()
                 self._restore(snap)
@@ -552,6 +674,8 @@ class DecodeEngine:
                 self._step_body()
                 info.max_actual_seq_len += 1
         self._check_device_errors()
+        if self._lp is not None:
+            self.last_logprobs = TokenLogprobs(self._lp.chosen[:, 1:], self._lp.top_logprobs[:, 1:], self._lp.top_ids[:, 1:])
         return self._out[:, 1:]
 
     def _check_device_errors(self) -> None:
@@ -572,6 +696,8 @@ class DecodeEngine:
                                    "broke its contract)")
 
     def _snapshot(self):
+        # The log-probability buffers (_lp) have no place here: the warm-up step and the capture write the very column
+        # (_step, which IS restored) that the first replay writes again, with the same values.
         info = self.info
         return (self._input_ids.clone(), self._positions.clone(), info.cur_select_index.clone(),
                 info.b_seq_len.clone(), self._step.clone(), self._out.clone(),

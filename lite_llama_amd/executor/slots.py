@@ -122,7 +122,7 @@ class StepGraphs:
                 self.model(ids, pos, info)
         torch.cuda.current_stream().wait_stream(side)
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
+        with L.graph_capture(graph):
             out = self.model(ids, pos, info)
         for kv, k in zip(self.kv_buffer, kept):
             kv[rows] = k

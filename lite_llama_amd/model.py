@@ -645,14 +645,27 @@ class CausalLM(nn.Module):
         """``[batch, seq]`` ids -> ``[batch, seq, vocab]`` fp16 logits.  ``logits_rows`` (extension:
         flat token indices) restricts the lm_head to those rows -- prefill only needs the last
         prompt position of every sequence, not ``batch*seq*vocab`` logits."""
+        hidden_states = self.final_hidden_states(input_ids, position_ids, atten_info)
+        if logits_rows is not None:
+            hidden_states = hidden_states.view(-1, hidden_states.shape[-1])[logits_rows]
+        return self.logits_from_hidden(hidden_states)
+
+    @torch.no_grad()
+    def final_hidden_states(self, input_ids, position_ids, atten_info):
+        """First half of :meth:`forward`: ``[batch, seq]`` ids -> the normalised final hidden states ``[batch, seq, hidden]``
+        (everything up to and including the final norm)."""
         hidden_states = self.embed_tokens(input_ids)
         position_embeddings = self.rotary_emb(hidden_states, position_ids)
         residual = None
         for i, layer in enumerate(self.layers):
             hidden_states, residual = layer(hidden_states, atten_info, i, position_embeddings, residual)
         hidden_states, _ = add_norm(hidden_states, residual, self.norm_weight, self.eps)
-        if logits_rows is not None:
-            hidden_states = hidden_states.view(-1, hidden_states.shape[-1])[logits_rows]
+        return hidden_states
+
+    @torch.no_grad()
+    def logits_from_hidden(self, hidden_states):
+        """Second half of :meth:`forward`: normalised hidden rows ``[..., hidden]`` -> logits ``[..., vocab]`` (the lm_head);
+        callers that need the logits of many rows take them a bounded number of rows at a time."""
         if hidden_states.is_cuda and not os.environ.get("LL_LM_HEAD_LIBRARY"):
             from .kernels.quantization import dense16_linear, dense16_rows_linear, dense16_rows_wins
             rows = hidden_states.numel() // hidden_states.shape[-1]

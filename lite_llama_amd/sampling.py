@@ -1,9 +1,12 @@
 """Sampling step after the hot path -- mirror of lite_llama/engine/sampler.py: greedy argmax
 (:227-228,264), HuggingFace-style repetition penalty (:77-115) and temperature + nucleus sampling
 (:118-137), as HIP kernels so the decode step stays on one stream (the reference's nucleus path is
-softmax + a full-vocabulary sort + cumsum + multinomial per step)."""
+softmax + a full-vocabulary sort + cumsum + multinomial per step).  ``token_logprobs`` (extension: the reference
+reports no probabilities) is the third kernel of the row: log-probability of a token and the top-k alternatives."""
 
 from __future__ import annotations
+
+from dataclasses import dataclass
 
 import torch
 
@@ -35,6 +38,92 @@ def greedy_argmax(logits: torch.Tensor) -> torch.Tensor:
         "greedy_argmax",
     )
     return out.view(logits.shape[:-1])
+
+MAX_TOP_LOGPROBS = 20
+
+
+@dataclass
+class TokenLogprobs:
+    """Log-probabilities of ``T`` tokens per row under the model's own distribution (log-softmax of the raw logits).
+    ``chosen [rows, T]`` fp32: the named token's (None when none was named); ``top_logprobs [rows, T, k]`` fp32 and
+    ``top_ids [rows, T, k]`` int64: the ``k`` most likely tokens, ordered by (logit descending, token id ascending)."""
+
+    chosen: torch.Tensor | None
+    top_logprobs: torch.Tensor
+    top_ids: torch.Tensor
+
+    def cumulative(self, lengths: torch.Tensor | None = None) -> torch.Tensor:
+        """``[rows]``: the sum of ``chosen`` over the first ``lengths[i]`` columns of row ``i`` (all columns by default) --
+        a sample's cumulative log-probability, a scored text's log-likelihood."""
+        if self.chosen is None:
+            raise ValueError("no token was named: there is no chosen log-probability to add up")
+        if lengths is None:
+            return self.chosen.sum(dim=1)
+        cols = torch.arange(self.chosen.shape[1], device=self.chosen.device).unsqueeze(0)
+        keep = cols < lengths.to(self.chosen.device).reshape(-1, 1)
+        return torch.where(keep, self.chosen, torch.zeros_like(self.chosen)).sum(dim=1)
+
+
+def token_logprobs(logits: torch.Tensor, token_ids: torch.Tensor | None = None, top_k: int = 0, *,
+                   out: TokenLogprobs | None = None, column: torch.Tensor | None = None) -> TokenLogprobs:
+    """``logits [rows, vocab]`` (fp16 / bf16 / fp32) -> :class:`TokenLogprobs` of ``token_ids [rows]`` (int64, optional)
+    and the ``top_k`` (0 .. 20) most likely tokens, in one read of the logits (csrc/logprobs.hip).  Without ``out`` the
+    result has ``T = 1``.  ``out``: buffers ``[rows, T]`` / ``[rows, T, top_k]`` to write into, at the column held by the
+    one-element int64 device tensor ``column`` (column 0 without it) -- the column is read on the device, so a launch
+    captured in a hipGraph follows a counter that the graph itself advances.  An id outside ``[0, vocab)`` gives NaN."""
+    top_k = int(top_k)
+    if not 0 <= top_k <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"top_k must be in 0 .. {MAX_TOP_LOGPROBS}, got {top_k}")
+    if logits.dim() != 2 or logits.shape[1] < 1:
+        raise ValueError("logits must be [rows, vocab]")
+    rows, vocab = logits.shape
+    if top_k > vocab:
+        raise ValueError(f"top_k {top_k} exceeds the vocabulary {vocab}")
+    if token_ids is None and top_k == 0:
+        raise ValueError("nothing to compute: name token_ids, ask for top_k > 0, or both")
+    if token_ids is not None and (token_ids.dtype != torch.int64 or token_ids.numel() != rows):
+        raise ValueError(f"token_ids must be int64 with one id per row of logits ({rows})")
+    if column is not None and (column.dtype != torch.int64 or column.numel() != 1):
+        raise ValueError("column must be a one-element int64 tensor")
+    if column is not None and out is None:
+        raise ValueError("column addresses the buffers of out")
+    if out is not None:
+        ch, tl, ti = out.chosen, out.top_logprobs, out.top_ids
+        if token_ids is not None and (ch is None or ch.dim() != 2 or ch.shape[0] != rows or ch.dtype != torch.float32
+                                      or ch.stride(1) != 1):
+            raise ValueError("out.chosen must be float32 [rows, T] with unit column stride")
+        t = ch.shape[1] if token_ids is not None else tl.shape[1]
+        if top_k > 0 and (tl.shape != (rows, t, top_k) or ti.shape != (rows, t, top_k) or tl.dtype != torch.float32
+                          or ti.dtype != torch.int64 or tl.stride()[1:] != (top_k, 1) or ti.stride()[1:] != (top_k, 1)):
+            raise ValueError("out.top_logprobs (float32) / out.top_ids (int64) must be [rows, T, top_k], columns packed")
+        if t < 1:
+            raise ValueError("out has no column")
+    L.require_cuda(logits, token_ids, column, *(() if out is None else (out.chosen, out.top_logprobs, out.top_ids)))
+    code = L.dtype_code(logits.dtype)
+    dev = logits.device
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    if out is None:
+        t = 1
+        out = TokenLogprobs(torch.empty(rows, 1, dtype=torch.float32, device=dev) if token_ids is not None else None,
+                            torch.empty(rows, 1, top_k, dtype=torch.float32, device=dev),
+                            torch.empty(rows, 1, top_k, dtype=torch.int64, device=dev))
+    if rows == 0:
+        return out
+    ids = None if token_ids is None else token_ids.reshape(-1).contiguous()
+    need = L.lib().ll_token_logprobs_scratch_bytes(rows, vocab, top_k)
+    if need < 0:
+        L.check(int(need), "token_logprobs")
+    scratch = torch.empty(need // 4, dtype=torch.int32, device=dev)
+    ch = out.chosen if token_ids is not None else None
+    L.check(
+        L.lib().ll_token_logprobs(L.ptr(ch), out.top_logprobs.data_ptr() if top_k else 0,
+                                  out.top_ids.data_ptr() if top_k else 0, logits.data_ptr(), L.ptr(ids), L.ptr(column),
+                                  rows, vocab, logits.stride(0), top_k, t, ch.stride(0) if ch is not None else 0,
+                                  out.top_logprobs.stride(0) if top_k else 0, out.top_ids.stride(0) if top_k else 0,
+                                  code, scratch.data_ptr(), need, L.stream_ptr()),
+        "token_logprobs")
+    return out
 
 
 def apply_repetition_penalty(logits: torch.Tensor, token_ids: torch.Tensor, mask: torch.Tensor, penalty) -> torch.Tensor:
