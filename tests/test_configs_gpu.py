@@ -20,6 +20,7 @@ import torch
 import torch.multiprocessing as mp
 
 from oracle import oracle as O
+from tests import _moe_ref as R
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -50,12 +51,11 @@ H5, I5, E5, TOPK5 = 2048, 768, 128, 8
 
 
 def _fp8_experts(seed, inter=I5, rows=None):
-    """Random e4m3 expert weights + 128 x 128 block scales in the checkpoint format (weight_scale_inv)."""
+    """Random e4m3 expert weights + 128 x 128 block scales in the checkpoint format (weight_scale_inv): codes ~ N(0, 1),
+    scales (U(0, 1) + 0.5) / sqrt(K) -- dequantised weights ~ N(0, 1 / K), so a block's output is of order 1."""
     g = torch.Generator().manual_seed(seed)
-    w1 = (torch.randn(E5, 2 * inter, H5, generator=g) * 0.6).to(torch.float8_e4m3fn).view(torch.uint8)
-    w2 = (torch.randn(E5, H5, inter, generator=g) * 0.6).to(torch.float8_e4m3fn).view(torch.uint8)
-    s1 = torch.rand(E5, 2 * inter // 128, H5 // 128, generator=g) * 0.02 + 0.01
-    s2 = torch.rand(E5, H5 // 128, inter // 128, generator=g) * 0.02 + 0.01
+    w1, s1 = R.fp8_block_experts(E5, 2 * inter, H5, g)
+    w2, s2 = R.fp8_block_experts(E5, H5, inter, g)
     return w1, w2, s1, s2
 
 
@@ -63,7 +63,7 @@ def _fp8_experts(seed, inter=I5, rows=None):
 def test_config5_fused_moe_fp8_block_vs_oracle(T):
     g = torch.Generator().manual_seed(50 + T)
     w1, w2, s1, s2 = _fp8_experts(5)
-    x = (torch.randn(T, H5, generator=g) / H5**0.5 * 4).half()
+    x = torch.randn(T, H5, generator=g).half()
     ids = torch.stack([torch.randperm(E5, generator=g)[:TOPK5] for _ in range(T)])
     wts = torch.softmax(torch.randn(T, TOPK5, generator=g), dim=-1).half()
     out = K().fused_moe(x.to(DEV), w1.to(DEV), w2.to(DEV), wts.to(DEV), ids.to(DEV), w1_scale=s1.to(DEV),
@@ -71,7 +71,14 @@ def test_config5_fused_moe_fp8_block_vs_oracle(T):
     assert out.shape == (T, H5) and torch.isfinite(out).all()
     sample = list(range(T)) if T <= 4 else [0, 17, 31, 63]  # the oracle dequantises one expert per slot
     ref = O.fused_moe(x[sample], w1, w2, wts[sample], ids[sample], w1_scale=s1, w2_scale=s2, group_n=128, group_k=128)
+    ref64 = R.moe_ref64(x[sample], w1, w2, wts[sample], ids[sample], w1_scale=s1, w2_scale=s2, w1_group=(128, 128),
+                        w2_group=(128, 128))
+    R.assert_has_signal(ref64, 2e-2)
     close(out[sample], ref, 2e-2)
+    yard = R.moe_error(ref, ref64)  # the oracle's own distance from float64; the kernel gets 4 x (tests/_moe_ref.py)
+    assert yard <= 5e-3
+    err = R.assert_moe_close(out[sample], ref64, 4 * yard)
+    print(f"config 5 fused_moe T {T}: kernel {err:.2e} oracle {yard:.2e} ratio {err / yard:.2f}")
 
 
 def _moe_block(tp_rank=0, tp=1, seed=7):
@@ -112,7 +119,7 @@ def _moe_block(tp_rank=0, tp=1, seed=7):
 
 def _moe_input(T=64):
     g = torch.Generator().manual_seed(99)
-    return (torch.randn(T, H5, generator=g) / H5**0.5 * 4).half()
+    return torch.randn(T, H5, generator=g).half()
 
 
 def test_config5_full_width_moe_block_vs_oracle():
@@ -131,7 +138,17 @@ def test_config5_full_width_moe_block_vs_oracle():
     with torch.no_grad():
         w_hip, ids_hip = blk._route(x.to(DEV))[:2]
     assert torch.equal(ids_hip[sample].cpu().sort(-1).values, ids.sort(-1).values)  # same experts chosen
+    grids = dict(w1_scale=s1, w2_scale=s2, w1_group=(128, 128), w2_group=(128, 128))
+    ref64 = R.moe_ref64(x[sample], w1, w2, w.half(), ids, **grids)
+    R.assert_has_signal(ref64, 2e-2)
     close(out[sample], ref, 2e-2)
+    yard = R.moe_error(ref, ref64)  # the oracle's own distance from float64; the kernel gets 4 x (tests/_moe_ref.py)
+    assert yard <= 5e-3
+    # the experts against float64 on the routing the block really used (the router kernels have exact tests of their own; a
+    # routed weight may differ from torch's by an fp16 ulp, which is not the grouped GEMM's error)
+    routed64 = R.moe_ref64(x[sample], w1, w2, w_hip[sample], ids_hip[sample], **grids)
+    err = R.assert_moe_close(out[sample], routed64, 4 * yard)
+    print(f"config 5 block: kernel {err:.2e} oracle {yard:.2e} ratio {err / yard:.2f}")
 
 
 def _tp_moe_worker(rank, world, port, q):

@@ -14,6 +14,7 @@ import torch
 
 from oracle import oracle as O
 from tests import _golden as G
+from tests import _moe_ref as R
 import lite_llama_amd._lib as L_
 
 pytestmark = pytest.mark.gpu
@@ -988,14 +989,20 @@ def test_fused_moe_golden(name):
 @pytest.mark.parametrize("num_experts,top_k", [(8, 2), (128, 8)])
 def test_fused_moe_oracle(num_tokens, num_experts, top_k):
     hidden, inter = 256, 128
-    x = (torch.randn(num_tokens, hidden) / hidden**0.5).half()
+    x = torch.randn(num_tokens, hidden).half()  # activations ~ N(0, 1), weights ~ N(0, 1 / K): outputs of order 1
     w1 = (torch.randn(num_experts, 2 * inter, hidden) / hidden**0.5).half()
     w2 = (torch.randn(num_experts, hidden, inter) / inter**0.5).half()
     ids = torch.randint(0, num_experts, (num_tokens, top_k))
     wts = torch.softmax(torch.randn(num_tokens, top_k), dim=-1).half()
     ref = O.fused_moe(x, w1, w2, wts, ids)
+    ref64 = R.moe_ref64(x, w1, w2, wts, ids)
+    R.assert_has_signal(ref64, 2e-2)
     out = K().fused_moe(x.to(DEV), w1.to(DEV), w2.to(DEV), wts.to(DEV), ids.to(DEV))
     close(out, ref, 2e-2)
+    yard = R.moe_error(ref, ref64)  # the oracle's own distance from float64; the kernel gets 4 x (tests/_moe_ref.py)
+    assert yard <= 5e-3
+    err = R.assert_moe_close(out, ref64, 4 * yard)
+    print(f"fused_moe f16 T {num_tokens} E {num_experts}: kernel {err:.2e} oracle {yard:.2e} ratio {err / yard:.2f}")
 
 
 def test_fused_moe_routing_weight_and_quant():
@@ -1027,7 +1034,7 @@ def test_fused_moe_prefill_sized_input_128_row_blocks_equal_64_row_blocks_and_or
     FM = importlib.import_module("lite_llama_amd.kernels.fused_moe")  # (the package attribute of that name is the function)
     num_tokens, num_experts, top_k, hidden, inter = 1100, 4, 2, 256, 128
     g = torch.Generator().manual_seed(77)
-    x = (torch.randn(num_tokens, hidden, generator=g) / hidden**0.5).half()
+    x = torch.randn(num_tokens, hidden, generator=g).half()
     w1 = torch.randn(num_experts, 2 * inter, hidden, generator=g) / hidden**0.5
     w2 = torch.randn(num_experts, hidden, inter, generator=g) / inter**0.5
     ids = torch.randint(0, num_experts, (num_tokens, top_k), generator=g)
@@ -1039,12 +1046,13 @@ def test_fused_moe_prefill_sized_input_128_row_blocks_equal_64_row_blocks_and_or
         (q1, s1), (q2, s2) = O.quantize_int8_per_channel(w1), O.quantize_int8_per_channel(w2)
         ws, kw = (q1, q2), dict(w1_scale=s1, w2_scale=s2, group_n=1, group_k=hidden)
     else:
-        q1 = (w1 * 8).to(torch.float8_e4m3fn).view(torch.uint8)
-        q2 = (w2 * 8).to(torch.float8_e4m3fn).view(torch.uint8)
-        s1 = (torch.rand(num_experts, 2 * inter // 128, hidden // 128, generator=g) + 0.5) / 8
-        s2 = (torch.rand(num_experts, hidden // 128, inter // 128, generator=g) + 0.5) / 8
+        (q1, s1), (q2, s2) = R.fp8_block_experts(num_experts, 2 * inter, hidden, g), R.fp8_block_experts(num_experts, hidden, inter, g)
         ws, kw = (q1, q2), dict(w1_scale=s1, w2_scale=s2, group_n=128, group_k=128)
     ref = O.fused_moe(x, ws[0], ws[1], wts, ids, **kw)
+    ref64 = R.moe_ref64(x, ws[0], ws[1], wts, ids, **R.groups_of(kw))
+    R.assert_has_signal(ref64, 2e-2)
+    yard = R.moe_error(ref, ref64)
+    assert yard <= 5e-3
     dkw = {k: (v.to(DEV) if torch.is_tensor(v) else v) for k, v in kw.items()}
     blocks = []
     real = FM._moe_gemm
@@ -1057,6 +1065,8 @@ def test_fused_moe_prefill_sized_input_128_row_blocks_equal_64_row_blocks_and_or
     big = K().fused_moe(x.to(DEV), ws[0].to(DEV), ws[1].to(DEV), wts.to(DEV), ids.to(DEV), **dkw)
     assert blocks and all(b == 128 for b in blocks), blocks
     close(big, ref, 2e-2)
+    err = R.assert_moe_close(big, ref64, 4 * yard)
+    print(f"fused_moe 128-row blocks {fmt}: kernel {err:.2e} oracle {yard:.2e} ratio {err / yard:.2f}")
     blocks.clear()
     monkeypatch.setattr(FM, "_block_m", lambda n: 64)
     half = K().fused_moe(x[:500].to(DEV), ws[0].to(DEV), ws[1].to(DEV), wts[:500].to(DEV), ids[:500].to(DEV), **dkw)  # < 256 rows / expert
@@ -1065,10 +1075,7 @@ def test_fused_moe_prefill_sized_input_128_row_blocks_equal_64_row_blocks_and_or
     assert torch.equal(half, big500)
 
 
-def _interleave_rows(w):
-    e, two_i = w.shape[0], w.shape[1]
-    i = two_i // 2
-    return torch.stack((w[:, :i], w[:, i:]), dim=2).reshape(e, two_i, *w.shape[2:]).contiguous()
+_interleave_rows = R.interleave_rows
 
 
 @pytest.mark.parametrize("fmt", ["f16", "fp8_channel", "int8_channel", "fp8_block"])
@@ -1079,32 +1086,40 @@ def test_fused_moe_with_interleaved_gate_up_equals_the_two_launch_form(fmt, num_
     for fp16 / per-channel fp8 / per-channel int8 experts and for 128 x 128 fp8 blocks re-expressed as per-row scales."""
     hidden, inter = 256, 256
     g = torch.Generator().manual_seed(num_tokens + num_experts)
-    x = (torch.randn(num_tokens, hidden, generator=g) / hidden**0.5).half().to(DEV)
+    x = torch.randn(num_tokens, hidden, generator=g).half().to(DEV)
     w1 = (torch.randn(num_experts, 2 * inter, hidden, generator=g) / hidden**0.5)
     w2 = (torch.randn(num_experts, hidden, inter, generator=g) / inter**0.5)
     ids = torch.randint(0, num_experts, (num_tokens, top_k), generator=g).to(DEV)
     wts = torch.softmax(torch.randn(num_tokens, top_k, generator=g), dim=-1).half().to(DEV)
     if fmt == "f16":
+        stacked = (w1.half(), w2.half(), {})
         a = K().fused_moe(x, w1.half().to(DEV), w2.half().to(DEV), wts, ids)
         b = K().fused_moe(x, _interleave_rows(w1.half()).to(DEV), w2.half().to(DEV), wts, ids, w1_interleaved=True)
     elif fmt in ("fp8_channel", "int8_channel"):
         qf = O.quantize_fp8_per_channel if fmt.startswith("fp8") else O.quantize_int8_per_channel
         q1, s1 = qf(w1)
         q2, s2 = qf(w2)
+        stacked = (q1, q2, dict(w1_scale=s1, w2_scale=s2, group_n=1, group_k=hidden))
         kw = dict(w2_scale=s2.to(DEV), group_n=1, group_k=hidden)
         a = K().fused_moe(x, q1.to(DEV), q2.to(DEV), wts, ids, w1_scale=s1.to(DEV), **kw)
         b = K().fused_moe(x, _interleave_rows(q1).to(DEV), q2.to(DEV), wts, ids, w1_scale=_interleave_rows(s1).to(DEV),
                           w1_interleaved=True, **kw)
     else:
-        q1 = (w1 * 8).to(torch.float8_e4m3fn).view(torch.uint8)
-        q2 = (w2 * 8).to(torch.float8_e4m3fn).view(torch.uint8)
-        s1 = (torch.rand(num_experts, 2 * inter // 128, hidden // 128, generator=g) + 0.5) / 8
-        s2 = (torch.rand(num_experts, hidden // 128, inter // 128, generator=g) + 0.5) / 8
+        (q1, s1), (q2, s2) = R.fp8_block_experts(num_experts, 2 * inter, hidden, g), R.fp8_block_experts(num_experts, hidden, inter, g)
+        stacked = (q1, q2, dict(w1_scale=s1, w2_scale=s2, group_n=128, group_k=128))
         a = K().fused_moe(x, q1.to(DEV), q2.to(DEV), wts, ids, w1_scale=s1.to(DEV), w2_scale=s2.to(DEV), group_n=128, group_k=128)
         rows = _interleave_rows(s1.repeat_interleave(128, dim=1)[:, : 2 * inter])
         b = K().fused_moe(x, _interleave_rows(q1).to(DEV), q2.to(DEV), wts, ids, w1_scale=rows.to(DEV), w2_scale=s2.to(DEV),
                           group_n=128, group_k=128, w1_group=(1, 128), w2_group=(128, 128), w1_interleaved=True)
     assert torch.equal(a, b)
+    # and both are the block: float64 reference of the stacked layout, the oracle's own error as the yardstick
+    ref = O.fused_moe(x.cpu(), stacked[0], stacked[1], wts.cpu(), ids.cpu(), **stacked[2])
+    ref64 = R.moe_ref64(x, stacked[0], stacked[1], wts, ids, **R.groups_of(stacked[2]))
+    R.assert_has_signal(ref64, 2e-2)
+    yard = R.moe_error(ref, ref64)
+    assert yard <= 5e-3
+    err = R.assert_moe_close(b, ref64, 4 * yard)
+    print(f"fused_moe interleaved {fmt} T {num_tokens}: kernel {err:.2e} oracle {yard:.2e} ratio {err / yard:.2f}")
 
 
 @pytest.mark.parametrize("slots,experts,block", [(512, 128, 32), (8, 8, 16), (1024, 1024, 64), (1, 128, 16), (777, 60, 32)])
