@@ -442,6 +442,27 @@ int ll_decode_advance(int64_t* out, int64_t out_stride, int64_t* step, const int
                       int32_t* b_seq_len, const int32_t* b_req_idx, int32_t* table,
                       int64_t table_stride_b, int64_t table_stride_s, int batch, void* stream);
 
+/* ll_decode_advance with per-row stopping (csrc/decode_stop.hip; executor/stopping.py states the semantics): a row that
+ * finished emits and is fed pad_token and advances nothing; a running row finishes on a stop id (reason 1), on a stop
+ * sequence completed as the tail of out[i, 0 .. step] (2) or on max_tokens[i] returned tokens (3).  stop_ids: int64
+ * [n_stop_ids <= LL_STOP_MAX_IDS]; stop_seqs: int64 [n_stop_seqs <= LL_STOP_MAX_SEQS][LL_STOP_MAX_SEQ_LEN], each row's
+ * first stop_seq_lens[q] entries; max_tokens: int32 [batch] or NULL; finished / lengths / reasons: int32 [batch];
+ * running: int32 [1], the rows still running after the step.  out has out_cols columns, a table row table_cols.
+ * cur_select_index NULL = the paged form: rows and table are left to ll_kv_paged_extend, followed by
+ * ll_decode_stop_redirect (finished rows write their K/V into the junk block, first row junk_row). */
+#define LL_STOP_MAX_IDS 32
+#define LL_STOP_MAX_SEQS 16
+#define LL_STOP_MAX_SEQ_LEN 8
+int ll_decode_stop_advance(int64_t* out, int64_t out_stride, int64_t out_cols, int64_t* step,
+                           const int64_t* next_tokens, int64_t* input_ids, int64_t* positions,
+                           int32_t* cur_select_index, int32_t* b_seq_len, const int32_t* b_req_idx, int32_t* table,
+                           int64_t table_stride_b, int64_t table_stride_s, int64_t table_cols, const int64_t* stop_ids,
+                           int n_stop_ids, const int64_t* stop_seqs, const int32_t* stop_seq_lens, int n_stop_seqs,
+                           const int32_t* max_tokens, int64_t pad_token, int32_t* finished, int32_t* lengths,
+                           int32_t* reasons, int32_t* running, int batch, void* stream);
+int ll_decode_stop_redirect(int32_t* cur_select_index, const int32_t* finished, int64_t junk_row, int block_size,
+                            int batch, void* stream);
+
 /* ---- device-side KV row allocator -------------------------------------------
  * Replaces the search of executor/kv_cache_manager.py:219-267 (``nonzero`` over the use-count
  * vector + two ``.item()`` reads = three device synchronisations per call) with three stream-ordered

@@ -89,6 +89,8 @@ SIGNATURES = {
     "ll_moe_router": [P, P, P, P, P, L, I, L, L, L, I, I, I, I, P, P, P, P, P],
     "ll_argmax": [P, P, L, L, L, I, P],
     "ll_decode_advance": [P, L, P, P, P, P, P, P, P, P, L, L, I, P],
+    "ll_decode_stop_advance": [P, L, L, P, P, P, P, P, P, P, P, L, L, L, P, I, P, P, I, P, L, P, P, P, P, I, P],
+    "ll_decode_stop_redirect": [P, P, L, I, I, P],
     "ll_slot_advance": [P, P, P, P, P, P, P, L, L, I, I, P],
     "ll_kv_alloc_scratch_bytes": [L],
     "ll_kv_alloc": [P, L, L, I, P, P, P, P, P],

@@ -9,7 +9,12 @@ MI355X-first differences from the reference (extensions, not parity changes):
     decode step is a single ``hipGraphLaunch`` with no host work in between (the reference
     replays only the forward and does 5 host-issued copies + sampler + index update per step);
   * the graph is also captured under tensor parallelism (RCCL all-reduces are capturable);
-    the reference disables graphs for TP>1 (model_runner.py:260-266).
+    the reference disables graphs for TP>1 (model_runner.py:260-266);
+  * the reference's loop has no EOS stop; ``decode(stop=StopCriteria(...))`` ends rows at stop ids, stop sequences and
+    per-row ``max_tokens`` -- the decision is taken on the device inside the captured step (csrc/decode_stop.hip in
+    ``ll_decode_advance``'s place, executor/stopping.py), finished rows are frozen, the results say where and why each
+    row ended (``last_lengths`` / ``last_finish_reasons``) and the loop ends early once every row has, without a host
+    synchronisation per step.  Without ``stop`` the loop is the reference's: lockstep, ``max_new_tokens`` steps.
 """
 
 from __future__ import annotations
@@ -23,6 +28,7 @@ import torch
 from .. import _lib as L
 from ..kernels import update_kv_index
 from ..sampling import MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, greedy_argmax, token_logprobs
+from .stopping import RunningWatch, StopCriteria, StopState, redirect_finished, stop_advance
 
 
 @dataclass
@@ -152,6 +158,11 @@ class DecodeEngine:
         self._prefill_logprobs = None
         self._logprobs_k = None
         self._lp = None
+        # stopping (extension): per-row lengths / finish reasons / the steps run of the last decode, when it had ``stop``
+        self.last_lengths: torch.Tensor | None = None
+        self.last_finish_reasons: torch.Tensor | None = None
+        self.last_steps_run: int | None = None
+        self._stop: StopState | None = None
         if hasattr(model, "rotary_emb") and torch.device(device).type == "cuda":
             model.rotary_emb.ensure(max_seq_len + 1, device, model.embed_tokens.weight.dtype)
 
@@ -515,7 +526,9 @@ class DecodeEngine:
         self._input_ids = first_tokens.view(b, 1).clone()
         # column 0 holds the token sampled by the prefill step: it is part of the generated span the repetition
         # penalty looks at from the second token on (llm_engine.py:168-176: GeneratedSpan over tokens[:, :cur_pos])
-        self._out = torch.zeros(b, max_new_tokens + 1, dtype=torch.long, device=dev)
+        # with ``stop`` the columns of steps never run (early exit) read as the pad, like those of finished rows
+        pad = 0 if self._stop is None else self._stop.pad
+        self._out = torch.full((b, max_new_tokens + 1), pad, dtype=torch.long, device=dev)
         self._out[:, 0] = first_tokens.view(b)
         self._step = torch.ones(1, dtype=torch.long, device=dev)
         self._row_base = torch.arange(b, device=dev) * (max_new_tokens + 1)
@@ -558,6 +571,20 @@ class DecodeEngine:
         has the engine's own dtypes, else the reference-shaped sequence of tensor ops."""
         info, b = self.info, self._batch
         t = info.b_req_tokens_table
+        if self._stop is not None:
+            # the same bookkeeping for the rows still running, plus the stop decision: one launch in ll_decode_advance's
+            # place (bump pool) / in place of the tensor ops below (paged pool; a finished row's unchanged length pops
+            # nothing in the append, and its K/V row is pointed at the junk block)
+            if self.paged:
+                stop_advance(self._out, self._step, nxt, self._input_ids, self._positions, None, info.b_seq_len, None,
+                             None, self._stop)
+                self.pool.append(info.b_req_idx, info.b_seq_len, t, out=info.cur_select_index)
+                redirect_finished(info.cur_select_index, self._stop, (self.pool.num_blocks - 1) * self.pool.block_size,
+                                  self.pool.block_size)
+            else:
+                stop_advance(self._out, self._step, nxt, self._input_ids, self._positions, info.cur_select_index,
+                             info.b_seq_len, info.b_req_idx, t, self._stop)
+            return
         if self.paged:
             self._out.view(-1).scatter_(0, self._row_base + self._step, nxt)
             self._step += 1
@@ -589,7 +616,7 @@ class DecodeEngine:
     @torch.no_grad()
     def decode(self, first_tokens: torch.Tensor, max_new_tokens: int, use_graph: bool = True,
                warmup_steps: int = 0, on_step=None, sampling=None, steps_per_graph: int = 1,
-               logprobs: int | None = None) -> torch.Tensor:
+               logprobs: int | None = None, stop: StopCriteria | None = None) -> torch.Tensor:
         """Generate ``max_new_tokens`` greedy tokens per row; returns ``[B, max_new_tokens]``.
 
         With ``use_graph`` the step is captured once (``max_actual_seq_len`` baked as the final
@@ -604,11 +631,26 @@ class DecodeEngine:
         ``k`` most likely alternatives under the model's own distribution (log-softmax of the raw logits: before repetition
         penalty, temperature and nucleus filter); ``self.last_logprobs`` then holds them, column ``t`` describing returned
         token ``[:, t]``.  The returned tokens are the same either way.
+        ``stop`` (extension, :class:`StopCriteria`; ``None``: the step holds exactly the launches it holds without it):
+        rows end at a stop id, a stop sequence or their ``max_tokens`` -- decided on the device inside the step (captured
+        with it, executor/stopping.py).  ``self.last_lengths`` / ``self.last_finish_reasons`` (int32 ``[B]``) then say where
+        and why each row ended, the returned tokens hold ``pad_token_id`` at and beyond a row's length (``last_logprobs``
+        its initial values there), and the loop ends early once every row has: every ``check_every`` steps the host
+        enqueues a copy of the running-row count to pinned memory and waits only for the copy enqueued one interval
+        earlier; ``self.last_steps_run`` is the number of steps issued.  Rows still running are not affected by the others'
+        stopping: their tokens are those of a decode without ``stop``.
         """
         self._logprobs_k = _check_logprobs(logprobs)
         self.last_logprobs = None
+        self.last_lengths = self.last_finish_reasons = self.last_steps_run = None
+        self._stop = None
+        if stop is not None:
+            stop.validate(self.model.geo.vocab_size, self._batch)
+            self._stop = StopState(stop, first_tokens, self.device)
         self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty
         self._begin_decode(first_tokens, max_new_tokens)
+        watch = RunningWatch(self._stop) if stop is not None and stop.check_every > 0 else None
+        steps_run = max_new_tokens
         info = self.info
         final_len = info.max_actual_seq_len + max_new_tokens
         if final_len > self.max_seq_len:
@@ -666,6 +708,9 @@ class DecodeEngine:
                 else:
                     graph.replay()
                     i += 1
+                if watch is not None and watch.all_finished(i):
+                    steps_run = i
+                    break
         else:
             for i in range(max_new_tokens):
                 if on_step is not None:
@@ -673,7 +718,19 @@ class DecodeEngine:
                 info.max_actual_seq_len = int(info.max_actual_seq_len)  # eager: exact value
                 self._step_body()
                 info.max_actual_seq_len += 1
+                if watch is not None and watch.all_finished(i + 1):
+                    steps_run = i + 1
+                    break
         self._check_device_errors()
+        if self._stop is not None:
+            st = self._stop
+            self.last_lengths, self.last_finish_reasons, self.last_steps_run = st.lengths, st.reasons, steps_run
+            if self._lp is not None:
+                # finished rows kept computing: their columns at and beyond the length go back to the initial values
+                gone = torch.arange(max_new_tokens + 1, device=self.device).unsqueeze(0) > st.lengths.view(-1, 1)
+                self._lp.chosen.masked_fill_(gone, 0.0)
+                self._lp.top_logprobs.masked_fill_(gone.unsqueeze(-1), 0.0)
+                self._lp.top_ids.masked_fill_(gone.unsqueeze(-1), -1)
         if self._lp is not None:
             self.last_logprobs = TokenLogprobs(self._lp.chosen[:, 1:], self._lp.top_logprobs[:, 1:], self._lp.top_ids[:, 1:])
         return self._out[:, 1:]
@@ -701,7 +758,8 @@ class DecodeEngine:
         info = self.info
         return (self._input_ids.clone(), self._positions.clone(), info.cur_select_index.clone(),
                 info.b_seq_len.clone(), self._step.clone(), self._out.clone(),
-                info.b_req_tokens_table.clone(), self.pool.snapshot() if self.paged else None)
+                info.b_req_tokens_table.clone(), self.pool.snapshot() if self.paged else None,
+                None if self._stop is None else [t.clone() for t in self._stop.tensors()])
 
     def _restore(self, snap):
         info = self.info
@@ -714,8 +772,12 @@ class DecodeEngine:
         info.b_req_tokens_table.copy_(snap[6])
         if self.paged:
             self.pool.restore(snap[7])
+        if self._stop is not None:
+            for t, saved in zip(self._stop.tensors(), snap[8]):
+                t.copy_(saved)
 
 
 from .chunking import ChunkPlan, plan_prefill_chunks  # noqa: E402,F401
 from .slots import DEFAULT_BATCH_SIZES, DEFAULT_SEQ_LEN_BUCKETS, SlotBatch, SlotRunner, StepGraphs, slot_advance  # noqa: E402,F401
 from .kv_cache_manager import KVCacheManager  # noqa: E402,F401
+from .stopping import MAX_STOP_SEQUENCE_LEN, MAX_STOP_SEQUENCES, MAX_STOP_TOKEN_IDS  # noqa: E402,F401
