@@ -663,6 +663,27 @@ int ll_token_logprobs(float* chosen, float* top_logprobs, int64_t* top_ids, cons
                       int64_t top_logprobs_stride, int64_t top_ids_stride, int dtype, void* scratch,
                       int64_t scratch_bytes, void* stream);
 
+/* ---- constrained decoding over a token automaton (csrc/constrained.hip; executor/constraints.py states the semantics) --
+ * The automaton is CSR over token ids, all int32 on the device: offsets [num_states + 1], tokens [edges] strictly
+ * ascending inside a state, next_states [edges].  states: int32 [batch], one per row, moved in place.  finished (optional,
+ * int32 [batch]): rows with finished[b] != 0 keep their state.  error: int32 [1], sticky; bit 1: ll_constraint_advance met
+ * a token its row's state does not allow (the state is left), bit 2: a state outside [0, num_states).
+ * ll_constrained_argmax: out[b] (int64) = the token of the edge of states[b] with the largest logit (stored value compared
+ *   as fp32; ties: the lowest token id; all -inf: the first edge), states[b] = that edge's next state.  One launch; reads
+ *   only the allowed tokens' logits.  logits [batch, vocab], F16 / BF16 / F32, row stride in elements.
+ * ll_constraint_mask: out[b, :] = -inf except the entries states[b] allows, which are copied bit for bit; out != logits,
+ *   same dtype.  States are not moved.
+ * ll_constraint_advance: states[b] follows chosen[b] (int64 [batch]). */
+int ll_constrained_argmax(int64_t* out, int32_t* states, const void* logits, const int32_t* offsets,
+                          const int32_t* tokens, const int32_t* next_states, const int32_t* finished, int32_t* error,
+                          int64_t batch, int64_t vocab, int64_t stride, int num_states, int dtype, void* stream);
+int ll_constraint_mask(void* out, const void* logits, const int32_t* states, const int32_t* offsets,
+                       const int32_t* tokens, int32_t* error, int64_t batch, int64_t vocab, int64_t logits_stride,
+                       int64_t out_stride, int num_states, int dtype, void* stream);
+int ll_constraint_advance(int32_t* states, const int64_t* chosen, const int32_t* offsets, const int32_t* tokens,
+                          const int32_t* next_states, const int32_t* finished, int32_t* error, int64_t batch,
+                          int num_states, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

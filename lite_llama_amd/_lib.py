@@ -123,6 +123,9 @@ SIGNATURES = {
     "ll_argmax_split": [P, P, L, L, L, I, P, I, P],
     "ll_token_logprobs_scratch_bytes": [L, L, I],
     "ll_token_logprobs": [P, P, P, P, P, P, L, L, L, I, L, L, L, L, I, P, L, P],
+    "ll_constrained_argmax": [P, P, P, P, P, P, P, P, L, L, L, I, I, P],
+    "ll_constraint_mask": [P, P, P, P, P, P, L, L, L, L, I, I, P],
+    "ll_constraint_advance": [P, P, P, P, P, P, P, L, I, P],
 }
 
 _RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints",

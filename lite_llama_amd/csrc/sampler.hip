@@ -274,7 +274,9 @@ __global__ __launch_bounds__(1024) void top_p_sample_kernel(int64_t* __restrict_
       const float o = __shfl_up(incl, off, 64);
       if (lane >= off) incl += o;
     }
-    const unsigned long long kb = __ballot(keep);
+    // the fallback names a token that carries mass: with top_p = 1 tau is 0, so zero-mass tokens (e == 0: a -inf or an
+    // underflowed logit) count as kept ties, and one of them after the last positive token must not be the answer
+    const unsigned long long kb = __ballot(keep && e > 0.f);
     if (kb) last_kept = i0 + (63 - __builtin_clzll(kb));
     const unsigned long long hit = __ballot(keep && acc_run + incl > target);
     if (hit && !overflow) {

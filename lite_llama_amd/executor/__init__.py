@@ -27,7 +27,9 @@ import torch
 
 from .. import _lib as L
 from ..kernels import update_kv_index
-from ..sampling import MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, greedy_argmax, token_logprobs
+from ..sampling import (MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, apply_repetition_penalty, greedy_argmax, sample_top_p,
+                        token_logprobs)
+from .constraints import ConstrainedRows, constrained_argmax, constraint_advance, constraint_mask
 from .stopping import RunningWatch, StopCriteria, StopState, redirect_finished, stop_advance
 
 
@@ -163,6 +165,8 @@ class DecodeEngine:
         self.last_finish_reasons: torch.Tensor | None = None
         self.last_steps_run: int | None = None
         self._stop: StopState | None = None
+        # constrained decoding (extension): the rows' automaton states of the running prefill / decode, when it has ``constraint``
+        self._constraint: ConstrainedRows | None = None
         if hasattr(model, "rotary_emb") and torch.device(device).type == "cuda":
             model.rotary_emb.ensure(max_seq_len + 1, device, model.embed_tokens.weight.dtype)
 
@@ -170,7 +174,8 @@ class DecodeEngine:
     @torch.no_grad()
     def prefill(self, prompt_ids: torch.Tensor, prompt_lens: torch.Tensor | None = None, sampling=None,
                 chunk_size: int | None = None, shared_prefix_ids: torch.Tensor | None = None,
-                num_samples: int | None = None, logprobs: int | None = None) -> torch.Tensor:
+                num_samples: int | None = None, logprobs: int | None = None,
+                constraint: ConstrainedRows | None = None) -> torch.Tensor:
         """``prompt_ids [B, Lp]`` (right-padded) -> next token per row ``[B]``: greedy, or -- with ``sampling`` -- drawn by
         the same sampler as every later token (llm_engine.py:168-176: the prefill step samples like a decode step; no
         token has been generated yet, so the repetition penalty has nothing to act on).  ``chunk_size`` (extension): run
@@ -182,8 +187,15 @@ class DecodeEngine:
         prompt ``i``; every prompt is prefilled and cached once, see :meth:`_prefill_samples`.  ``logprobs`` (extension, an
         integer ``k >= 0``): ``self.first_logprobs`` is left holding the log-probability of every returned token and the
         ``k`` most likely alternatives (``T = 1``), under the model's own distribution -- the log-softmax of the raw logits,
-        before temperature and nucleus filter; on every route, since all of them end in :meth:`_first_tokens`."""
+        before temperature and nucleus filter; on every route, since all of them end in :meth:`_first_tokens`.
+        ``constraint`` (extension, :class:`ConstrainedRows` with one row per returned token -- ``B * n`` with
+        ``num_samples``): the rows are put back to their start states, the returned token is the best (greedy) or a drawn
+        (``sampling``) token among those the start state allows, and the states are advanced once; pass the same object to
+        :meth:`decode` to continue.  On every route too."""
         b = prompt_ids.shape[0]
+        self._constraint = None
+        if constraint is not None:
+            constraint.validate(self.model.geo.vocab_size, b * (int(num_samples) if num_samples is not None else 1))
         self._prefill_logprobs = _check_logprobs(logprobs)
         self.first_logprobs = None
         if num_samples is not None:
@@ -196,6 +208,9 @@ class DecodeEngine:
             if int(num_samples) < 1 or b * int(num_samples) > self.max_batch:
                 raise ValueError(f"num_samples {num_samples} x {b} prompts must give between 1 and max_batch "
                                  f"{self.max_batch} rows")
+        if constraint is not None:
+            constraint.reset()
+            self._constraint = constraint
         self.info.shared_prefix_len, self.info.shared_prefix_req = 0, 0
         if num_samples is not None:
             return self._prefill_samples(prompt_ids, prompt_lens, sampling, chunk_size, int(num_samples))
@@ -279,11 +294,18 @@ class DecodeEngine:
         return self._first_tokens(last.repeat_interleave(n, dim=0), sampling)
 
     def _first_tokens(self, last: torch.Tensor, sampling) -> torch.Tensor:
-        if sampling is None or sampling.temperature == 0.0:
+        rows = self._constraint
+        greedy = sampling is None or sampling.temperature == 0.0
+        if rows is not None and greedy:
+            tokens = constrained_argmax(last, rows)
+        elif greedy:
             tokens = greedy_argmax(last)
         else:
             uniform = torch.rand(last.shape[0], device=self.device)
-            tokens = Sampler().sample(last, sampling, None, uniform=uniform).view(-1)
+            drawn_from = last if rows is None else constraint_mask(last, rows)
+            tokens = Sampler().sample(drawn_from, sampling, None, uniform=uniform).view(-1)
+            if rows is not None:
+                constraint_advance(rows, tokens)
         if self._prefill_logprobs is not None:
             self.first_logprobs = token_logprobs(last, tokens, self._prefill_logprobs)
         return tokens
@@ -555,8 +577,11 @@ class DecodeEngine:
         (repetition penalty over the tokens generated so far, then temperature + nucleus sampling) on
         the HIP kernels; the uniform numbers come from ``torch.rand`` (graph-safe Philox)."""
         sp = self._sampling
+        rows = self._constraint
+        # rows that were finished when the step began keep their automaton state
+        finished = None if self._stop is None else self._stop.finished
         if sp is None:
-            return greedy_argmax(logits)
+            return greedy_argmax(logits) if rows is None else constrained_argmax(logits, rows, finished)
         b = self._batch
         generated = None
         if sp.repetition_penalty != 1.0:
@@ -564,7 +589,17 @@ class DecodeEngine:
             mask = torch.arange(span, device=self.device).unsqueeze(0) < self._step  # [1, span] -> rows share it
             generated = _Span(self._out, mask.expand(b, span))
         uniform = torch.rand(b, device=self.device) if sp.temperature != 0.0 else None
-        return Sampler().sample(logits, sp, generated, uniform=uniform).view(-1)
+        if rows is None:
+            return Sampler().sample(logits, sp, generated, uniform=uniform).view(-1)
+        # constrained: the penalty acts on the raw logits as it does above; greedy rows pick among the allowed tokens of
+        # the (penalised) logits in one launch, sampled ones draw from a copy with the disallowed tokens at -inf
+        if generated is not None:
+            logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, sp.repetition_penalty)
+        if sp.temperature == 0.0:
+            return constrained_argmax(logits, rows, finished)
+        nxt = sample_top_p(constraint_mask(logits, rows), sp.temperature, sp.top_p, uniform).view(-1)
+        constraint_advance(rows, nxt, finished)
+        return nxt
 
     def _advance(self, nxt: torch.Tensor) -> None:
         """record -> feed back -> positions/lengths/KV rows += -> token table: one launch when the state
@@ -616,7 +651,8 @@ class DecodeEngine:
     @torch.no_grad()
     def decode(self, first_tokens: torch.Tensor, max_new_tokens: int, use_graph: bool = True,
                warmup_steps: int = 0, on_step=None, sampling=None, steps_per_graph: int = 1,
-               logprobs: int | None = None, stop: StopCriteria | None = None) -> torch.Tensor:
+               logprobs: int | None = None, stop: StopCriteria | None = None,
+               constraint: ConstrainedRows | None = None) -> torch.Tensor:
         """Generate ``max_new_tokens`` greedy tokens per row; returns ``[B, max_new_tokens]``.
 
         With ``use_graph`` the step is captured once (``max_actual_seq_len`` baked as the final
@@ -639,7 +675,16 @@ class DecodeEngine:
         enqueues a copy of the running-row count to pinned memory and waits only for the copy enqueued one interval
         earlier; ``self.last_steps_run`` is the number of steps issued.  Rows still running are not affected by the others'
         stopping: their tokens are those of a decode without ``stop``.
+        ``constraint`` (extension, :class:`ConstrainedRows`; ``None``: the step holds exactly the launches it holds without
+        it): every row emits only tokens its automaton state allows and the state follows them, inside the step (captured
+        with it, executor/constraints.py) -- greedy steps select and advance in one launch in the argmax's place, sampled
+        steps mask a copy of the logits, draw, and advance.  The rows continue from ``constraint.states`` (where a
+        ``prefill(constraint=...)`` left them); afterwards ``constraint.states`` describes the valid tokens of every row
+        (rows finished by ``stop`` no longer move).  ``logprobs`` keeps reporting the model's own distribution.
         """
+        self._constraint = None
+        if constraint is not None:
+            constraint.validate(self.model.geo.vocab_size, self._batch)
         self._logprobs_k = _check_logprobs(logprobs)
         self.last_logprobs = None
         self.last_lengths = self.last_finish_reasons = self.last_steps_run = None
@@ -647,6 +692,7 @@ class DecodeEngine:
         if stop is not None:
             stop.validate(self.model.geo.vocab_size, self._batch)
             self._stop = StopState(stop, first_tokens, self.device)
+        self._constraint = constraint
         self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty
         self._begin_decode(first_tokens, max_new_tokens)
         watch = RunningWatch(self._stop) if stop is not None and stop.check_every > 0 else None
@@ -751,6 +797,11 @@ class DecodeEngine:
                 raise RuntimeError(f"paged KV pool reported error bits {err:#x} (1: a call found too few free blocks, "
                                    "2: a request outgrew its block-table / token-table row, 4: a fork "
                                    "broke its contract)")
+        if self._constraint is not None:
+            err = int(self._constraint.error.item())
+            if err:
+                raise RuntimeError(f"constrained decoding reported error bits {err:#x} (1: a row was to follow a token its "
+                                   "automaton state does not allow, 2: a row's state lies outside the automaton)")
 
     def _snapshot(self):
         # The log-probability buffers (_lp) have no place here: the warm-up step and the capture write the very column
@@ -759,7 +810,8 @@ class DecodeEngine:
         return (self._input_ids.clone(), self._positions.clone(), info.cur_select_index.clone(),
                 info.b_seq_len.clone(), self._step.clone(), self._out.clone(),
                 info.b_req_tokens_table.clone(), self.pool.snapshot() if self.paged else None,
-                None if self._stop is None else [t.clone() for t in self._stop.tensors()])
+                None if self._stop is None else [t.clone() for t in self._stop.tensors()],
+                None if self._constraint is None else [t.clone() for t in self._constraint.tensors()])
 
     def _restore(self, snap):
         info = self.info
@@ -775,9 +827,13 @@ class DecodeEngine:
         if self._stop is not None:
             for t, saved in zip(self._stop.tensors(), snap[8]):
                 t.copy_(saved)
+        if self._constraint is not None:
+            for t, saved in zip(self._constraint.tensors(), snap[9]):
+                t.copy_(saved)
 
 
 from .chunking import ChunkPlan, plan_prefill_chunks  # noqa: E402,F401
 from .slots import DEFAULT_BATCH_SIZES, DEFAULT_SEQ_LEN_BUCKETS, SlotBatch, SlotRunner, StepGraphs, slot_advance  # noqa: E402,F401
 from .kv_cache_manager import KVCacheManager  # noqa: E402,F401
 from .stopping import MAX_STOP_SEQUENCE_LEN, MAX_STOP_SEQUENCES, MAX_STOP_TOKEN_IDS  # noqa: E402,F401
+from .constraints import TokenAutomaton, from_choices, from_transitions, union  # noqa: E402,F401
