@@ -1325,20 +1325,20 @@ def test_repetition_penalty_matches_reference(dt):
 
 
 def _check_draws(logits, temperature, top_p, dist, n_u=257):
-    """Every draw must be the inverse CDF (token order) of ``dist`` at its uniform number; draws whose
-    number sits within 1e-5 of an interval edge are exempt (fp32 vs fp64 summation order)."""
+    """Every draw must lie inside its window of the fp64 nucleus of the stored logits (``accept`` of tests/_sampler_ref.py,
+    margin 1e-5 for fp32 against fp64 summation order): the token is in the nucleus, carries mass, and its interval of the
+    token-order CDF holds the uniform number.  No draw is exempt."""
     from lite_llama_amd.sampling import sample_top_p
+    from tests import _sampler_ref as R
     b = logits.shape[0]
-    cdf = torch.cumsum(dist.double(), dim=-1)
-    cdf = cdf / cdf[:, -1:]
-    for k in range(n_u):
-        u = torch.full((b,), (k + 0.37) / n_u)
-        tok = sample_top_p(logits.to(DEV), temperature, top_p, uniform=u.to(DEV)).view(-1).cpu()
-        want = (cdf > u.double().view(-1, 1)).float().argmax(dim=-1)
-        edge = (cdf - u.double().view(-1, 1)).abs().min(dim=-1).values < 1e-5
-        ok = (tok == want) | edge
-        assert bool(ok.all()), (k, tok.tolist(), want.tolist())
-        assert bool((dist[torch.arange(b), tok] > 0).all())  # never outside the nucleus
+    p, before = R.nucleus64(logits, temperature.cpu(), top_p.cpu())
+    us = torch.tensor([(k + 0.37) / n_u for k in range(n_u)])
+    toks = torch.stack([sample_top_p(logits.to(DEV), temperature, top_p, uniform=torch.full((b,), float(u)).to(DEV)).view(-1).cpu()
+                        for u in us])
+    for r in range(b):
+        ok = R.accept(toks[:, r], us, (p[r], before[r], float(top_p[r])), 1e-5)
+        assert bool(ok.all()), (r, us[~ok].tolist(), toks[:, r][~ok].tolist())
+        assert bool((dist[r, toks[:, r]] > 0).all())  # never outside the nucleus
 
 
 def test_top_p_sampling_matches_reference_distribution():
