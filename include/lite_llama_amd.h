@@ -642,6 +642,26 @@ int ll_repetition_penalty(void* out, const void* logits, const int64_t* token_id
 int ll_sample_top_p(int64_t* out, const void* logits, const float* temperature, const float* top_p,
                     const float* uniform, const void* greedy, int64_t batch, int64_t vocab,
                     int64_t stride, int dtype, void* stream);
+/* ll_sample_filtered: ll_sample_top_p with a top-k and a min-p filter, in one launch (csrc/sampler_filters.hip).  Per row,
+ * with p = softmax(stored logit / T), T > 0:
+ *   1. top-k (top_k[b]; <= 0 or >= vocab: off): v = the k-th largest STORED logit of the row; the survivors are all tokens
+ *      with logit >= v, so every token tied with the k-th survives.  Defined on stored values: exact for every input.
+ *      -inf sorts last; if the k-th value is -inf everything survives.  Zero-mass tokens are never drawn.
+ *   2. top-p over the survivors: tokens ordered by (probability descending, index ascending), before_i = the survivors'
+ *      mass strictly before i; token i is kept iff before_i <= top_p * (mass of the survivors); ties at the threshold are
+ *      rationed in ascending index order, as ll_sample_top_p does it.
+ *   3. min-p (0 <= min_p[b] <= 1; 0: off): a kept token is dropped if p_i < min_p * p_max, evaluated as e_i < min_p in
+ *      fp32 with e_i = exp2((logit_i - max) * log2(e) / T) (the maximum's e is exactly 1).  It acts AFTER the nucleus has
+ *      been chosen: the nucleus mass is that of the top-k survivors, not of the min-p survivors.
+ *   4. draw: inverse CDF in token order over what is left at uniform[b]: the first token whose cumulative kept mass
+ *      strictly exceeds u * Z; on rounding at u ~ 1 the last kept token that carries mass.  greedy[b] != 0: first argmax.
+ * The maximum survives all three filters.  top_k int32 [batch] or NULL (off), min_p float [batch] or NULL (off; an entry
+ * that is negative or NaN is off as well, one above 1 counts as 1); a row
+ * with both off draws exactly the token ll_sample_top_p draws.  Logits F16 / BF16 / F32, row stride in elements; status
+ * codes as ll_sample_top_p; no allocation, no host synchronisation, capturable.  NaN logits are out of scope. */
+int ll_sample_filtered(int64_t* out, const void* logits, const float* temperature, const float* top_p,
+                       const int32_t* top_k, const float* min_p, const float* uniform, const void* greedy,
+                       int64_t batch, int64_t vocab, int64_t stride, int dtype, void* stream);
 
 /* ---- token log-probabilities (the third kernel of the sampler row) -------------------------
  * Per row of logits [rows, vocab] (F16 / BF16 / F32, row stride in elements, unit column stride), with

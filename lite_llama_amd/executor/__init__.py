@@ -27,8 +27,8 @@ import torch
 
 from .. import _lib as L
 from ..kernels import update_kv_index
-from ..sampling import (MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, apply_repetition_penalty, greedy_argmax, sample_top_p,
-                        token_logprobs)
+from ..sampling import (MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, apply_repetition_penalty, greedy_argmax,
+                        sample_with_filters, token_logprobs)
 from .constraints import ConstrainedRows, constrained_argmax, constraint_advance, constraint_mask
 from .stopping import RunningWatch, StopCriteria, StopState, redirect_finished, stop_advance
 
@@ -597,7 +597,8 @@ class DecodeEngine:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, sp.repetition_penalty)
         if sp.temperature == 0.0:
             return constrained_argmax(logits, rows, finished)
-        nxt = sample_top_p(constraint_mask(logits, rows), sp.temperature, sp.top_p, uniform).view(-1)
+        # top_k / min_p of sp act on the masked copy: top-k counts among the allowed tokens
+        nxt = sample_with_filters(constraint_mask(logits, rows), sp, uniform).view(-1)
         constraint_advance(rows, nxt, finished)
         return nxt
 
@@ -681,6 +682,10 @@ class DecodeEngine:
         steps mask a copy of the logits, draw, and advance.  The rows continue from ``constraint.states`` (where a
         ``prefill(constraint=...)`` left them); afterwards ``constraint.states`` describes the valid tokens of every row
         (rows finished by ``stop`` no longer move).  ``logprobs`` keeps reporting the model's own distribution.
+        ``sampling`` may carry ``top_k`` (int) and ``min_p`` (float in [0, 1]) -- extension; absent, 0 and 0.0 are off and
+        the step holds exactly the launches it holds without them: the draw then runs ``ll_sample_filtered`` in
+        ``ll_sample_top_p``'s place (sampling.sample_filtered has the rule), here and in :meth:`prefill`; under a
+        ``constraint`` the filters see the masked copy, so top-k counts among the allowed tokens.
         """
         self._constraint = None
         if constraint is not None:
@@ -693,7 +698,7 @@ class DecodeEngine:
             stop.validate(self.model.geo.vocab_size, self._batch)
             self._stop = StopState(stop, first_tokens, self.device)
         self._constraint = constraint
-        self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty
+        self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty [/ top_k / min_p]
         self._begin_decode(first_tokens, max_new_tokens)
         watch = RunningWatch(self._stop) if stop is not None and stop.check_every > 0 else None
         steps_run = max_new_tokens

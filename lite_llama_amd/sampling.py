@@ -192,11 +192,71 @@ def sample_top_p(logits: torch.Tensor, temperature, top_p, uniform: torch.Tensor
     return out.view(batch, 1)
 
 
+def _filter_off(top_k, min_p) -> bool:
+    """Both filters off for every row, decided on the host without reading a tensor: ``None`` or Python scalars only."""
+    k_off = top_k is None or (not torch.is_tensor(top_k) and int(top_k) <= 0)
+    return k_off and (min_p is None or (not torch.is_tensor(min_p) and float(min_p) == 0.0))
+
+
+def sample_filtered(logits: torch.Tensor, temperature, top_p, top_k=0, min_p=0.0, uniform: torch.Tensor | None = None,
+                    greedy: torch.Tensor | None = None) -> torch.Tensor:
+    """:func:`sample_top_p` with a top-k and a min-p filter in the same single launch (csrc/sampler_filters.hip) -> int64
+    ``[batch, 1]``.  Per row: the ``top_k`` largest stored logits survive, with every token tied with the k-th
+    (``<= 0`` or ``>= vocab``: off); the nucleus of ``top_p`` is chosen among the survivors; a kept token whose probability
+    is below ``min_p`` times the largest one is then dropped (``0``: off); the draw is the inverse CDF in token order over
+    what is left.  ``top_k`` (int) and ``min_p`` (float in [0, 1]): scalars, per-row tensors, or ``None`` for off (the
+    entries of a tensor are not validated: a ``min_p`` entry that is negative or NaN is off, one above 1 counts as 1); the
+    other arguments as in :func:`sample_top_p`.  A row with both filters off draws the token ``sample_top_p`` draws."""
+    L.require_cuda(logits, uniform, greedy)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [batch, vocab]")
+    batch, vocab = logits.shape
+    if not torch.is_tensor(min_p) and min_p is not None and not 0.0 <= float(min_p) <= 1.0:
+        raise ValueError(f"min_p must be in [0, 1], got {min_p}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    dev = logits.device
+
+    def rows(v, dtype=torch.float32):
+        if v is None:
+            return None
+        if torch.is_tensor(v):
+            t = v.reshape(-1).to(device=dev, dtype=dtype)
+            return t.expand(batch).contiguous() if t.numel() == 1 else t.contiguous()
+        return torch.full((batch,), v, dtype=dtype, device=dev)
+
+    t, p, mp = rows(temperature), rows(top_p), rows(min_p)
+    if top_k is not None and not torch.is_tensor(top_k):
+        top_k = max(0, min(int(top_k), vocab))  # beyond the vocabulary is off, like vocab itself: fits int32
+    k = rows(top_k, torch.int32)
+    u = torch.rand(batch, device=dev) if uniform is None else uniform.reshape(-1).to(torch.float32).contiguous()
+    g = None if greedy is None else greedy.reshape(-1).to(torch.bool).contiguous()
+    if any(x is not None and x.numel() != batch for x in (t, p, k, mp, u, g)):
+        raise ValueError("per-row sampling knobs need one entry per row")
+    out = torch.empty(batch, dtype=torch.int64, device=dev)
+    L.check(
+        L.lib().ll_sample_filtered(out.data_ptr(), logits.data_ptr(), t.data_ptr(), p.data_ptr(), L.ptr(k), L.ptr(mp),
+                                   u.data_ptr(), L.ptr(g), batch, vocab, logits.stride(0), L.dtype_code(logits.dtype),
+                                   L.stream_ptr()),
+        "sample_filtered")
+    return out.view(batch, 1)
+
+
+def sample_with_filters(logits, params, uniform, greedy=None) -> torch.Tensor:
+    """The draw of :class:`Sampler`: ``top_k`` / ``min_p`` are read from ``params`` with the defaults 0 and 0.0 (the
+    reference's parameter objects lack them; ``None`` is off too); with both off this is :func:`sample_top_p`, the launch it has always been."""
+    top_k, min_p = getattr(params, "top_k", 0), getattr(params, "min_p", 0.0)
+    if _filter_off(top_k, min_p):
+        return sample_top_p(logits, params.temperature, params.top_p, uniform, greedy=greedy)
+    return sample_filtered(logits, params.temperature, params.top_p, top_k, min_p, uniform, greedy=greedy)
+
+
 class Sampler:
     """``Sampler.sample`` / ``sample_batched`` of the reference (sampler.py:199-270) on the kernels above.
     ``params``: any object with ``temperature``, ``top_p``, ``repetition_penalty`` (scalars for
     ``sample``; ``[batch, 1]`` tensors plus ``greedy`` / ``all_greedy`` / ``any_penalty`` for
-    ``sample_batched``); ``generated``: object with ``token_ids`` and ``mask``."""
+    ``sample_batched``) and, optionally, ``top_k`` / ``min_p`` (extension, default off: scalars or per-row tensors);
+    ``generated``: object with ``token_ids`` and ``mask``."""
 
     @torch.no_grad()
     def sample(self, logits, params, generated=None, uniform=None):
@@ -206,7 +266,7 @@ class Sampler:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, params.repetition_penalty)
         if params.temperature == 0.0:
             return greedy_argmax(logits).view(-1, 1)
-        return sample_top_p(logits, params.temperature, params.top_p, uniform)
+        return sample_with_filters(logits, params, uniform)
 
     @torch.no_grad()
     def sample_batched(self, logits, params, generated=None, uniform=None):
@@ -216,4 +276,4 @@ class Sampler:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, params.repetition_penalty)
         if params.all_greedy:
             return greedy_argmax(logits).view(-1, 1)
-        return sample_top_p(logits, params.temperature, params.top_p, uniform, greedy=params.greedy)
+        return sample_with_filters(logits, params, uniform, greedy=params.greedy)
