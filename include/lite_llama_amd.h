@@ -289,6 +289,11 @@ int ll_w4a16_matmul_prepacked(void* out, const void* x, const void* wpacked, con
  * [takes the launch 0 / 1, grid, row groups per workgroup, rbase, rrem, compute units assumed, LDS bytes, 0]; workgroup t owns the
  * 32-row groups [t * rbase + min(t, rrem), + rbase + (t < rrem)).  No device work. */
 int ll_w4a16_v4_plan(int64_t m, int64_t n, int64_t k, int group_size, int epilogue, int32_t* out8);
+/* Host-side introspection (no device work, changes no launch): which engine ll_w4a16_matmul_prepacked runs for this shape and
+ * epilogue -- 0 short-stream split-K planes (gemm_short.hip), 1 row-group loop (gemm_w4_v4.hip), 2 short-stream all-of-K form
+ * (gemm_short_full.hip), 3 unit loop (gemm_w4_v3.hip); -1: the launch is refused (ll_w4a16_prepacked_supported says no, or
+ * epilogue 2 with ll_w4a16_partials_count_ex == 0). */
+int ll_w4a16_engine_id(int64_t m, int64_t n, int64_t k, int group_size, int epilogue);
 
 /* The same product for MANY rows (prefill: m = batch x prompt tokens; w4a16.py:152-207 tiles M x N) over the same load-time
  * layouts: 256 x 256 x 64 MFMA tiles, the weight tile dequantised once per 256 rows (gemm_w4_prefill.hip).  epilogue 0: out

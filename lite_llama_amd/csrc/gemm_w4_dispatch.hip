@@ -44,6 +44,14 @@ extern "C" int ll_w4a16_partials_count(int64_t m, int64_t n, int64_t k, int grou
   return ll_w4a16_partials_count_ex(m, n, k, group_size, 2);
 }
 
+// Host-side introspection (tests; no device work, changes no launch): the W4Engine a launch of this shape and epilogue takes, -1 when
+// ll_w4a16_matmul_prepacked would refuse it (shape outside the engines, or a split-K partial launch that leaves no planes).
+extern "C" int ll_w4a16_engine_id(int64_t m, int64_t n, int64_t k, int group_size, int epilogue) {
+  if (!ll_w4a16_prepacked_supported(m, n, k, group_size)) return -1;
+  if ((epilogue & 3) == 2 && ll_w4a16_partials_count_ex(m, n, k, group_size, epilogue) == 0) return -1;
+  return (int)w4a16_engine(m, n, k, group_size, epilogue);
+}
+
 extern "C" int ll_w4a16_matmul_prepacked(void* out, const void* x, const void* wpacked, const void* spacked,
                                          const void* bias, int64_t m, int64_t n, int64_t k, int group_size,
                                          int64_t x_stride_m, float* workspace, int32_t* counters, int epilogue,

@@ -7,7 +7,8 @@
 //     1184 groups over 256 CUs) and a contiguous range of 128-k chunks -- ALL of K for the launches that write finished
 //     outputs.  No stream-K: no fp32 slabs written and read back (128 KB per CU and launch), no merge counters, no owner
 //     tail (~7 us of the 31-us gate|up launch), no unit walkers (the scalar state that spilled).  Split-K partial launches
-//     (o, down, q|k|v: epilogue 2) keep their k-slices and planes, only the body changes.
+//     (o, down, q|k|v: epilogue 2) stay on the short-stream engine / the unit loop by default; this file's body for them
+//     (same k-slices and planes) is compiled but taken only under LL_GEMM4 bit 1 (V4Knobs::on).
 //   * CONSUMERS.  Eight consumer waves = 4 k-QUARTERS of every chunk (two MFMA k-steps each) x 2 halves of the workgroup's row
 //     groups (3 + 2 of 5), both batch halves in one wave: every weight word is read from LDS and dequantised exactly once per
 //     workgroup, every activation fragment is read twice (v3: four times; 72 KB of operand reads per 128-row unit against

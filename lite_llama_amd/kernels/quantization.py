@@ -145,6 +145,17 @@ def w4a16_prepacked_supported(m: int, n: int, k: int, group_size: int) -> bool:
     return bool(L.lib().ll_w4a16_prepacked_supported(m, n, k, int(group_size)))
 
 
+_W4_ENGINES = ("short_partials", "row_groups", "short_full", "unit_loop")
+
+
+def w4a16_engine(m: int, n: int, k: int, group_size: int, epilogue: int = 0) -> str:
+    """Which pre-packed engine a launch of this shape and ``epilogue`` (the value ``ll_w4a16_matmul_prepacked`` is given) takes:
+    ``"short_partials"`` (gemm_short.hip), ``"row_groups"`` (gemm_w4_v4.hip), ``"short_full"`` (gemm_short_full.hip),
+    ``"unit_loop"`` (gemm_w4_v3.hip), or ``"none"`` when the launch is refused.  Host-side introspection: no device work."""
+    e = L.lib().ll_w4a16_engine_id(int(m), int(n), int(k), int(group_size), int(epilogue))
+    return _W4_ENGINES[e] if 0 <= e < len(_W4_ENGINES) else "none"
+
+
 def _launch_prepacked(out_ptr, a, m, n, k, packed_weight, packed_scales, bias, group_size, epilogue, what):
     """The decode-engine launch."""
     ws, cnt = L.gemm_workspace(a.device, m, n, k)
@@ -223,8 +234,11 @@ def w4a16_matmul_prepacked_rows(x, packed_weight, packed_scales, *, group_size: 
 def w4a16_matmul_partials(x, packed_weight, packed_scales, *, group_size: int = 128, _unit_loop_engine: bool = False):
     """Decode-step extension: the projection as ``S`` fp32 split-K partial sums (:class:`PartialSums`) for
     :func:`skip_rmsnorm_partials` to add up -- the GEMM has no cross-workgroup merge then.  ``None`` when the shape
-    is not served (the caller runs :func:`w4a16_matmul_prepacked`).  ``_unit_loop_engine`` (tests / tuning): the same planes
-    from the third-generation body (gemm_w4_v3.hip) instead of the row-group loop (gemm_w4_v4.hip)."""
+    is not served (the caller runs :func:`w4a16_matmul_prepacked`).  By default the planes come from the short-stream engine
+    (gemm_short.hip) when the weight stream is a few tens of KB per CU and from the unit loop (gemm_w4_v3.hip) otherwise; the
+    row-group loop (gemm_w4_v4.hip) takes split-K partial launches only under ``LL_GEMM4`` bit 1, which is off by default
+    (:func:`w4a16_engine` names the route).  ``_unit_loop_engine`` (tests / tuning): the unit loop's planes and its k-split
+    whatever the default route."""
     from .norm_act import PartialSums
     L.require_cuda(x, packed_weight, packed_scales)
     n, k = packed_weight.shape[0] * 128, packed_weight.shape[1] * 128

@@ -395,6 +395,54 @@ def test_row_group_engine_plan_assigns_every_row_group_once():
     assert plan(37888, 3584, 1 | (2 << 8))[0] == 0                         # a forced unit-loop tile width (tests / tuning)
 
 
+def test_w4a16_engine_names_the_route_the_plans_describe():
+    """``kernels.quantization.w4a16_engine`` (``ll_w4a16_engine_id``; host only) against the engines' own plan queries, on the
+    headline shapes and on the shapes of tests/test_w4a16_row_groups_gpu.py: "row_groups" exactly where ``ll_w4a16_v4_plan`` takes
+    the launch, "short_partials" exactly where ``ll_w4a16_short_plan`` does (epilogue 2), "short_full" where
+    ``ll_w4a16_short_full_plan`` does and the row-group loop does not; a forced tile width stays on the unit loop; split-K partial
+    launches never reach the row-group loop by default; refused launches are "none"."""
+    import ctypes
+    from lite_llama_amd import _lib
+    from lite_llama_amd.kernels.quantization import w4a16_engine
+
+    lib = _lib.lib()
+
+    def plan0(fn, *args):
+        out = (ctypes.c_int32 * 8)()
+        assert fn(*args, ctypes.cast(out, ctypes.c_void_p)) == 0
+        return out[0], out[5]
+
+    cus = plan0(lib.ll_w4a16_v4_plan, 64, 37888, 3584, 128, 0)[1]
+    widths = [32 * (3 * cus + 4), 128 * cus, 32 * (4 * cus + 4), 160 * cus]
+    shapes = [(m, n, k, 128) for m in (1, 32, 33, 64) for n, k in [(37888, 3584), (4608, 3584), (3584, 3584), (3584, 18944), (28672, 4096)]]
+    shapes += [(m, n, k, gs) for m in (1, 17, 33, 64) for n in widths for k, gs in [(128, 128), (384, 128), (1280, 128), (1280, 256)]]
+    shapes += [(64, 256, 256, 128), (64, 1024, 4608, 128), (16, 1024, 4608, 256), (64, 512, 1024, 128), (64, 512, 1024, 256)]
+    seen = set()
+    for m, n, k, gs in shapes:
+        for ep in (0, 1, 2):
+            eng = w4a16_engine(m, n, k, gs, ep)
+            seen.add(eng)
+            v4 = plan0(lib.ll_w4a16_v4_plan, m, n, k, gs, ep)[0]
+            ss = plan0(lib.ll_w4a16_short_plan, m, n, k, gs)[0]
+            sf = plan0(lib.ll_w4a16_short_full_plan, m, n, k, gs)[0]
+            assert (eng == "row_groups") == (v4 == 1), (m, n, k, gs, ep, eng)
+            if ep == 2:
+                planes = lib.ll_w4a16_partials_count_ex(m, n, k, gs, 2)
+                assert eng == ("none" if planes == 0 else "short_partials" if ss else "unit_loop"), (m, n, k, gs, eng)
+            else:
+                assert eng == ("row_groups" if v4 else "short_full" if sf else "unit_loop"), (m, n, k, gs, ep, eng)
+            for tb in (1, 2):
+                forced = w4a16_engine(m, n, k, gs, ep | (tb << 8))
+                assert forced == ("none" if ep == 2 and lib.ll_w4a16_partials_count_ex(m, n, k, gs, ep | (tb << 8)) == 0 else "unit_loop")
+    assert seen >= {"row_groups", "short_partials", "short_full", "unit_loop"}, seen
+    for n in widths:
+        for m in (1, 64):
+            assert w4a16_engine(m, n, 1280, 128) == w4a16_engine(m, n, 1280, 256, 1) == "row_groups"
+    assert w4a16_engine(64, 37888, 3584, 128, 1) == "row_groups" and w4a16_engine(64, 28672, 4096, 128, 1) == "row_groups"
+    assert w4a16_engine(65, 4608, 3584, 128) == "none" and w4a16_engine(64, 4608, 3584, 96) == "none"   # outside the decode engines
+    assert w4a16_engine(64, 100, 3584, 128) == "none"
+
+
 def test_int8_rows_regroup_only_their_leading_dimensions():
     """kernels/norm_act.py::Int8Rows stands in for the fp16 activations of a smoothquant block (the quantiser ran inside the
     norm launch): callers re-group its leading dimensions like a tensor's; the row width never changes."""

@@ -259,6 +259,38 @@ def test_short_stream_full_k_unpack_bit_exact_at_every_k_position():
             assert torch.equal(got, nib[:, k0:k0 + m].t().contiguous()), (m, k0)
 
 
+@pytest.mark.parametrize("gs", [128, 256])
+@pytest.mark.parametrize("route,n,k,m", [("unit_loop_tb1", 256, 256, 64), ("unit_loop_tb2", 256, 256, 64), ("short_full", 1024, 4608, 64),
+                                         ("short_full", 1024, 4608, 16), ("short_partials", 512, 1024, 64), ("unit_loop_planes", 512, 1024, 64)])
+def test_one_hot_rows_return_the_affine_weights_bit_for_bit_on_every_route(route, n, k, m, gs):
+    """The scale-1 one-hot tests above cannot see a scale or a zero read from the wrong row or group.  Here the weights carry a random
+    power-of-two scale and an integer zero per (row, group) (tests/_w4_ref.py::exact_case, groups of 128 and 256): with one-hot rows
+    the output -- or the fp32 sum of the planes -- IS ``dequant16[:, k0 : k0 + m].T``, bit for bit, at every k position, through the
+    unit loop at both tile widths, the all-of-K short-stream form, the short-stream planes and the unit loop's planes (the shapes of
+    the scale-1 tests; the route asserted with ``w4a16_engine``; the bias on the finished-output routes)."""
+    from tests import _w4_ref as R
+    qw, sc, zr, bias = (t.to(DEV) for t in R.exact_case(n, k, gs, seed=n + k + gs + m))
+    pw, ps = Q().pack_w4a16_weights(qw), Q().pack_w4a16_scales(sc, zr)
+    wt = R.dequant16(qw, sc, zr, gs).T
+    assert torch.equal(wt.T.float(), (R.unpack_int4(qw).float() - zr.repeat_interleave(gs, 1)) * sc.repeat_interleave(gs, 1))
+    epilogue, want_engine = {"unit_loop_tb1": (1 << 8, "unit_loop"), "unit_loop_tb2": (2 << 8, "unit_loop"), "short_full": (0, "short_full"),
+                             "short_partials": (2, "short_partials"), "unit_loop_planes": (2 | 0x100, "unit_loop")}[route]
+    assert Q().w4a16_engine(m, n, k, gs, epilogue) == want_engine
+    starts = list(range(0, k, m))
+    bad = torch.zeros(len(starts), dtype=torch.int64, device=DEV)
+    for i, k0 in enumerate(starts):
+        x = R.one_hot_rows(m, k, k0, DEV)
+        if epilogue & 2:
+            parts = Q().w4a16_matmul_partials(x, pw, ps, group_size=gs, _unit_loop_engine=route == "unit_loop_planes")
+            assert parts is not None
+            bad[i] = (parts.parts.sum(0) != wt[k0:k0 + m].float()).sum()  # one plane holds the term, the others exact zeros
+        else:
+            y = Q().w4a16_matmul_prepacked(x, pw, ps, group_size=gs, bias=bias, _tile_blocks=epilogue >> 8)
+            bad[i] = (y != wt[k0:k0 + m] + bias).sum()  # (q - z) * s + bias is an fp16 value: the fp16 add is exact
+    bad = bad.cpu()
+    assert not bool(bad.any()), {starts[i]: int(b) for i, b in enumerate(bad) if b}
+
+
 @pytest.mark.parametrize("M", [1, 17, 32, 33, 64])
 @pytest.mark.parametrize("N,K_,gs,swiglu", [(3584, 3584, 128, False), (1024, 3584, 128, False), (4608, 3584, 128, True), (9472, 3584, 128, True),
                                             (2048, 1536, 128, False), (4096, 4096, 256, False), (8192, 4096, 128, True), (512, 128, 128, False),
