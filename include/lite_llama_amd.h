@@ -313,6 +313,15 @@ int ll_w8a16_matmul(void* out, const void* x, const void* qweight, const float* 
                     const void* bias, int64_t m, int64_t n, int64_t k, int group_n, int64_t group_k,
                     int wfmt, int64_t x_stride_m, int64_t qw_stride_n, int64_t s_stride_n,
                     int64_t s_stride_k, float* workspace, int32_t* counters, void* stream);
+/* Host-side introspection (no device work, changes no launch): which engine ll_w8a16_matmul runs for this call, given 16-byte-
+ * aligned pointers and the workspace of ll_gemm_workspace -- 1 M-tiled (gemm_w8_prefill.hip; m > 64, n % 32 == 0, k % 64 == 0),
+ * 2 skinny split-K (gemm_w8_skinny.hip; m <= 64, n % 4 == 0, k % 128 == 0), 3 generic (gemm_wq.hip); 0: the call is refused
+ * (or m == 0).  Built from the predicates the engines' own launch functions apply, in the dispatcher's order. */
+int ll_w8a16_engine(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride_m, int64_t qw_stride_n);
+/* fp32 words of split-K partial planes the skinny engine wants in the workspace for (m, n, k): splits * m * n; 0 = a shape it
+ * does not take.  (ll_gemm_workspace already includes them.)  Its launch uses cps = ceil(chunks / splits) 128-k chunks per
+ * split, chunks = k / 128, and ceil(chunks / cps) planes. */
+int64_t ll_dense8_partial_words(int64_t m, int64_t n, int64_t k);
 
 /* ---- a10: smoothquant_matmul  (kernels/quantization/w8a8.py:151-217) ----------
  * step 1: per-row scale = absmax/127 (1.0 if 0), q = trunc(x/scale) int8;
@@ -339,6 +348,9 @@ int ll_w8_mtiled_supported(int64_t m, int64_t n, int64_t k, int wfmt, int64_t gr
  * ll_dense_partials_count: S for (shape, format, cap) -- 0 = not served; ll_dense_partials returns
  * the S it wrote (the same number), 0 when alignment rules decline the call, < 0 on error. */
 int ll_dense_partials_count(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits);
+/* Host-side introspection (no device work): the body ll_dense_partials runs for a served shape -- 1 the short-stream form
+ * (gemm_short_dense.hip), 2 the streaming split-K kernel (gemm_w8_skinny.hip); 0 where ll_dense_partials_count is 0. */
+int ll_dense_partials_form(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits);
 int ll_dense_partials(float* partials, const void* x, const void* w, const float* scales, int64_t m, int64_t n, int64_t k,
                       int group_n, int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride, int64_t s_stride_n,
                       int64_t s_stride_k, int max_splits, void* stream);

@@ -64,6 +64,8 @@ SIGNATURES = {
     "ll_w4a16_matmul_prepacked_mtiled": [P, P, P, P, P, L, L, L, I, L, I, P],
     "ll_w4a16_v3_plan": [L, L, L, I, I, P],
     "ll_w8a16_matmul": [P, P, P, P, P, L, L, L, I, L, I, L, L, L, L, P, P, P],
+    "ll_w8a16_engine": [L, L, L, L, I, L, L],
+    "ll_dense8_partial_words": [L, L, L],
     "ll_quantize_activations_int8": [P, P, P, L, L, L, P],
     "ll_dense16_matmul": [P, P, P, P, L, L, L, L, L, I, P, P],
     "ll_w8a8_rows_supported": [L, L, L, I],
@@ -71,6 +73,7 @@ SIGNATURES = {
     "ll_dense16_rows_supported": [L, L, L, I],
     "ll_dense16_rows_matmul": [P, P, P, P, L, L, L, L, L, I, I, P],
     "ll_dense_partials_count": [L, L, L, I, I],
+    "ll_dense_partials_form": [L, L, L, I, I],
     "ll_dense_partials": [P, P, P, P, L, L, L, I, L, I, L, L, L, L, I, P],
     "ll_skip_rmsnorm_q8": [P, P, P, P, P, I, P, P, P, P, P, L, L, F, P],
     "ll_w8a8_finish_swiglu": [P, P, I, P, P, L, L, P],
@@ -131,7 +134,7 @@ SIGNATURES = {
 }
 
 _RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints",
-                "ll_shared_prefix_workspace_floats", "ll_token_logprobs_scratch_bytes"}
+                "ll_shared_prefix_workspace_floats", "ll_token_logprobs_scratch_bytes", "ll_dense8_partial_words"}
 _lib = None
 
 

@@ -35,6 +35,8 @@ extern "C" int ll_dense8_try(void* out, const void* x, const void* w, const floa
                              const void* bias, int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n,
                              int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride, int64_t s_stride_n,
                              int64_t s_stride_k, void* partials, void* stream);
+// ... and what ll_dense8_try asks of a call besides its pointers (ll_w8a16_engine asks too)
+bool dense8_takes(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride);
 // its short-stream form (gemm_short_dense.hip)
 int sd_partials_slices(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits);
 int sd_launch(float* out, const void* x, const void* w, const float* scales, int64_t m, int64_t n, int64_t k, int group_n,
@@ -44,3 +46,5 @@ int sd_launch(float* out, const void* x, const void* w, const float* scales, int
 extern "C" int ll_w8_mtiled_try(void* out, const void* x, const void* w, const float* scales, const float* a_scale, const void* bias,
                                 int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n, int64_t group_k, int wfmt,
                                 int64_t x_stride, int64_t w_stride, int64_t s_stride_n, int64_t s_stride_k, void* stream);
+// ... and what it asks of a call besides its pointers (group_k already clamped to k; ll_w8a16_engine asks too)
+bool w8_mtiled_takes(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride);

@@ -293,15 +293,25 @@ extern "C" int ll_w8_mtiled_supported(int64_t m, int64_t n, int64_t k, int wfmt,
   return tiles < (1ll << 31) ? 1 : 0;
 }
 
+// Everything ll_w8_mtiled_try asks of a call except its pointers: the shape (ll_w8_mtiled_supported), the two row strides and the
+// 32-bit operand offsets they imply.  ONE definition, used by the launch below and by the route query ll_w8a16_engine (gemm_wq.hip).
+// group_k: already clamped to k.
+bool w8_mtiled_takes(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride) {
+  if (!ll_w8_mtiled_supported(m, n, k, wfmt, group_k)) return false;
+  const int eb = wfmt == 3 ? 1 : 2;  // bytes per activation element
+  if ((x_stride * eb) % 16 != 0 || w_stride % 16 != 0) return false;
+  if ((m - 1) * x_stride * eb + k * eb >= (1ll << 32) || (n - 1) * w_stride + k >= (1ll << 32)) return false;
+  return true;
+}
+
 // Returns 1 when the launch was issued, 0 when the shape / alignment is not served (nothing happened), < 0 on a launch error.
 extern "C" int ll_w8_mtiled_try(void* out, const void* x, const void* w, const float* scales, const float* a_scale, const void* bias,
                                 int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n, int64_t group_k, int wfmt,
                                 int64_t x_stride, int64_t w_stride, int64_t s_stride_n, int64_t s_stride_k, void* stream) {
   if (group_k <= 0 || group_k > k) group_k = k;
-  if (!ll_w8_mtiled_supported(m, n, k, wfmt, group_k)) return 0;
+  if (!w8_mtiled_takes(m, n, k, group_k, wfmt, x_stride, w_stride)) return 0;
   const int eb = wfmt == 3 ? 1 : 2;  // bytes per activation element
-  if ((x_stride * eb) % 16 != 0 || w_stride % 16 != 0 || !ll_aligned16(x) || !ll_aligned16(w) || !ll_aligned16(out)) return 0;
-  if ((m - 1) * x_stride * eb + k * eb >= (1ll << 32) || (n - 1) * w_stride + k >= (1ll << 32)) return 0;
+  if (!ll_aligned16(x) || !ll_aligned16(w) || !ll_aligned16(out)) return 0;
   if (wfmt == 3 && (!a_scale || !scales || !ll_aligned16(scales) || (acc_out && !ll_aligned16(acc_out)))) return 0;
   if (wfmt != 3 && !scales) return 0;
   if (bias && (reinterpret_cast<uintptr_t>(bias) & 7u)) return 0;

@@ -280,16 +280,25 @@ extern "C" int64_t ll_dense8_partial_words(int64_t m, int64_t n, int64_t k) {
   return (int64_t)d8_splits(n, k) * m * n;
 }
 
+// Everything ll_dense8_try asks of a call except its pointers (a workspace, 16-byte alignment): the shape, the two row strides
+// and the scale groups along k.  ONE definition, used by the launch below and by the route query ll_w8a16_engine (gemm_wq.hip).
+bool dense8_takes(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride) {
+  static const bool off = getenv("LL_DENSE8_OFF") != nullptr;  // A/B knob, read once
+  if (off || ll_dense8_partial_words(m, n, k) == 0) return false;
+  if (wfmt != D8_FP8 && wfmt != D8_I8 && wfmt != D8_I8I8) return false;
+  if (w_stride % 16 != 0) return false;
+  if (wfmt == D8_I8I8 ? (x_stride % 16 != 0) : (x_stride % 8 != 0 || (group_k < k && group_k % 64 != 0))) return false;
+  return true;
+}
+
 // wfmt: 1 fp8 e4m3 / 2 int8 (fp16 activations, block scales) / 3 int8 x int8 (per-token / per-channel scales).
 // Returns 1 when the launch was issued, 0 when the shape is not served (nothing happened), < 0 on a launch error.
 extern "C" int ll_dense8_try(void* out, const void* x, const void* w, const float* scales, const float* a_scale,
                              const void* bias, int32_t* acc_out, int64_t m, int64_t n, int64_t k, int group_n,
                              int64_t group_k, int wfmt, int64_t x_stride, int64_t w_stride, int64_t s_stride_n,
                              int64_t s_stride_k, void* partials, void* stream) {
-  static const bool off = getenv("LL_DENSE8_OFF") != nullptr;  // A/B knob, read once
-  if (off || !partials || ll_dense8_partial_words(m, n, k) == 0) return 0;
-  if (w_stride % 16 != 0 || !ll_aligned16(w) || !ll_aligned16(x) || !ll_aligned16(out) || !ll_aligned16(partials)) return 0;
-  if (wfmt == D8_I8I8 ? (x_stride % 16 != 0) : (x_stride % 8 != 0 || (group_k < k && group_k % 64 != 0))) return 0;
+  if (!partials || !dense8_takes(m, n, k, group_k, wfmt, x_stride, w_stride)) return 0;
+  if (!ll_aligned16(w) || !ll_aligned16(x) || !ll_aligned16(out) || !ll_aligned16(partials)) return 0;
   D8Params p{};
   p.part = partials; p.x = x; p.w = (const unsigned char*)w; p.scales = scales;
   p.m = m; p.n = n; p.k = k; p.x_stride = x_stride; p.w_stride = w_stride;
@@ -399,6 +408,14 @@ extern "C" int ll_dense_partials_count(int64_t m, int64_t n, int64_t k, int wfmt
   const int splits = d8_splits(n, k, kch, max_splits);
   const int cps = (chunks + splits - 1) / splits;
   return (chunks + cps - 1) / cps;
+}
+
+// Host-side introspection (no device work): which body ll_dense_partials runs for a served shape -- 1 the short-stream form
+// (gemm_short_dense.hip), 2 the streaming kernel of this file (dense8_kernel); 0: ll_dense_partials_count is 0.  The same two
+// questions, in the same order, as the launch below asks.
+extern "C" int ll_dense_partials_form(int64_t m, int64_t n, int64_t k, int wfmt, int max_splits) {
+  if (ll_dense_partials_count(m, n, k, wfmt, max_splits) == 0) return 0;
+  return sd_partials_slices(m, n, k, wfmt, max_splits) ? 1 : 2;
 }
 
 extern "C" int ll_dense_partials(float* partials, const void* x, const void* w, const float* scales, int64_t m, int64_t n,

@@ -359,6 +359,8 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void wgemm_kernel(const GemmParams
       for (int g = 0; g < NSG; ++g) {
         // zero scale -> zero weight for the k tail (the clamped loads read valid, finite data).
         // Integer AND masks, not selects: hipcc turns a float select into an exec-masked branch.
+        // (8-bit formats: this cuts whole 64-k halves; the half that straddles K is cut per MFMA step below, on the packed
+        // integer pair -- an integer select, v_cndmask.)
         const uint32_t gm = (kbase + g * (64 / NSG)) < K ? 0xFFFFFFFFu : 0u;
         if constexpr (FMT == FMT_W4) {
           sp[g] = pk_bcast(sreg[slot][g]) & gm;
@@ -394,13 +396,17 @@ __global__ __launch_bounds__(GEMM_THREADS, 4) void wgemm_kernel(const GemmParams
           const Q4& src = wreg[slot][s >> 1];
           const uint32_t w0 = (s & 1) ? src.z : src.x;
           const uint32_t w1 = (s & 1) ? src.w : src.y;
+          // Step s holds k = kbase + 8 s .. + 7 of this lane's half.  K need only be a multiple of 16 here, so the half that
+          // straddles K is cut per step, not per 64 k: past K the clamped loads have re-read real weights and real activations,
+          // and a scale of zero turns those weights into zeros (an integer select; K % 8 == 0: a step is in or out as a whole).
+          const uint32_t sps = (kbase + s * 8) < K ? sp[0] : 0u;
           uint32_t d0, d1, d2, d3;
           if constexpr (FMT == FMT_FP8) {
-            dequant_fp8(w0, sp[0], d0, d1);
-            dequant_fp8(w1, sp[0], d2, d3);
+            dequant_fp8(w0, sps, d0, d1);
+            dequant_fp8(w1, sps, d2, d3);
           } else {
-            dequant_i8(w0, sp[0], d0, d1);
-            dequant_i8(w1, sp[0], d2, d3);
+            dequant_i8(w0, sps, d0, d1);
+            dequant_i8(w1, sps, d2, d3);
           }
           wf = Q4{d0, d1, d2, d3};
         }
@@ -691,16 +697,36 @@ extern "C" int ll_w4a16_matmul(void* out, const void* x, const int32_t* qweight,
   return LL_ERR_SHAPE;
 }
 
-extern "C" int ll_w8a16_matmul(void* out, const void* x, const void* qweight, const float* scales,
-                               const void* bias, int64_t m, int64_t n, int64_t k, int group_n,
-                               int64_t group_k, int wfmt, int64_t x_stride_m, int64_t qw_stride_n,
-                               int64_t s_stride_n, int64_t s_stride_k, float* workspace,
-                               int32_t* counters, void* stream) {
+// What ll_w8a16_matmul asks of a call before it picks an engine; clamps group_k to k.  LL_OK or the error the entry returns.
+static int w8a16_check(int64_t m, int64_t n, int64_t k, int group_n, int64_t& group_k, int wfmt, int64_t x_stride_m,
+                       int64_t qw_stride_n) {
   if (wfmt != LL_W_FP8E4M3 && wfmt != LL_W_INT8) return LL_ERR_DTYPE;
   if (m < 0 || n <= 0 || k <= 0 || group_n <= 0 || group_k <= 0) return LL_ERR_SHAPE;
   if (group_k > k) group_k = k;
   if (group_k % 128 != 0 && group_k < k) return LL_ERR_SHAPE;  // w8a16.py:189-191
   if (k % 16 != 0 || x_stride_m % 8 != 0 || qw_stride_n % 16 != 0) return LL_ERR_SHAPE;
+  return LL_OK;
+}
+
+// Host-side introspection (no device work, changes no launch): the engine ll_w8a16_matmul runs for this call, given 16-byte-aligned
+// pointers and a workspace from ll_gemm_workspace -- 1 the M-tiled engine (gemm_w8_prefill.hip), 2 the skinny split-K engine
+// (gemm_w8_skinny.hip), 3 the generic engine (wgemm_kernel above); 0: the call is refused or m == 0.  Asked in the dispatcher's
+// order of the predicates the two *_try functions themselves apply (w8_mtiled_takes, dense8_takes).
+extern "C" int ll_w8a16_engine(int64_t m, int64_t n, int64_t k, int64_t group_k, int wfmt, int64_t x_stride_m,
+                               int64_t qw_stride_n) {
+  if (w8a16_check(m, n, k, 1, group_k, wfmt, x_stride_m, qw_stride_n) != LL_OK || m == 0) return 0;
+  const int wf = wfmt == LL_W_FP8E4M3 ? 1 : 2;
+  if (m > 64 && w8_mtiled_takes(m, n, k, group_k, wf, x_stride_m, qw_stride_n)) return 1;
+  if (dense8_takes(m, n, k, group_k, wf, x_stride_m, qw_stride_n)) return 2;
+  return 3;
+}
+
+extern "C" int ll_w8a16_matmul(void* out, const void* x, const void* qweight, const float* scales,
+                               const void* bias, int64_t m, int64_t n, int64_t k, int group_n,
+                               int64_t group_k, int wfmt, int64_t x_stride_m, int64_t qw_stride_n,
+                               int64_t s_stride_n, int64_t s_stride_k, float* workspace,
+                               int32_t* counters, void* stream) {
+  if (const int rc = w8a16_check(m, n, k, group_n, group_k, wfmt, x_stride_m, qw_stride_n)) return rc;
   if (!ll_aligned16(x) || !ll_aligned16(qweight)) return LL_ERR_ARG;
   if (m == 0) return LL_OK;
   if (m > 64) {  // prefill shapes (round 6): M x N tiled MFMA GEMM, the weight tile fetched once per 256 rows (gemm_w8_prefill.hip)

@@ -265,6 +265,21 @@ def w8_mtiled_supported(m: int, n: int, k: int, fmt: str, group_k: int | None = 
     return bool(L.lib().ll_w8_mtiled_supported(m, n, k, wf, int(k if group_k is None else min(group_k, k))))
 
 
+_W8_ENGINES = {1: "mtiled", 2: "skinny", 3: "generic"}
+
+
+def w8a16_engine(m: int, n: int, k: int, fmt: str, group_k: int | None = None, x_stride_m: int | None = None,
+                 qw_stride_n: int | None = None) -> str:
+    """Which engine a ``w8a16_matmul`` call of ``m`` rows takes: ``"mtiled"`` (gemm_w8_prefill.hip), ``"skinny"`` (the split-K
+    engine of gemm_w8_skinny.hip) or ``"generic"`` (gemm_wq.hip::wgemm_kernel); ``"none"`` when the call is refused.  ``fmt``:
+    "fp8" / "int8"; the row strides (elements of ``x``, bytes of ``qweight``) default to contiguous rows.  Assumes 16-byte-aligned
+    tensors.  Host-side introspection (``ll_w8a16_engine``): no device work."""
+    wf = {"fp8": L.LL_W_FP8E4M3, "int8": L.LL_W_INT8}[fmt]
+    e = L.lib().ll_w8a16_engine(int(m), int(n), int(k), int(k if group_k is None else min(group_k, k)), wf,
+                                int(k if x_stride_m is None else x_stride_m), int(k if qw_stride_n is None else qw_stride_n))
+    return _W8_ENGINES.get(e, "none")
+
+
 def w8a16_matmul(
     x: torch.Tensor,
     qweight: torch.Tensor,
@@ -275,7 +290,11 @@ def w8a16_matmul(
     bias: torch.Tensor | None = None,
 ) -> torch.Tensor:
     """``x @ dequant(qweight).T (+ bias)`` with uint8 (fp8-e4m3 bits) or int8 weights and one
-    fp32 scale per ``(group_n, group_k)`` weight block."""
+    fp32 scale per ``(group_n, group_k)`` weight block.  The scale is applied in fp16 inside the GEMM (one fp16 multiply of the
+    exactly widened code by ``fp16(s)``, for fp8 by ``fp16(s * 256)``, subnormals kept), so each weight is within
+    ``2**-10`` relative (``+ 2**-25``) of ``value(code) * s`` while that multiplier is a normal fp16 number and the product is
+    finite: ``2**-14 <= s`` (fp8: ``2**-22 <= s``) and ``|value(code) * s| < 65504``; below that range the scale loses precision
+    like ``2**-25 / s`` (fp8: ``2**-33 / s``) (DESIGN_NOTEBOOK.md 8.19)."""
     is_fp8 = qweight.dtype == torch.uint8
     if not is_fp8 and qweight.dtype != torch.int8:
         raise ValueError(f"qweight must be uint8 (fp8) or int8, got {qweight.dtype}")

@@ -620,7 +620,9 @@ def test_w4a16_float_zero_points_and_errors():
 
 
 # ------------------------------------------------------------------------------------- #
-# w8a16 (tol 1e-2; 8-bit widening exact)
+# w8a16 (tol 1e-2; 8-bit widening exact).  The three engines behind the entry are held to exact
+# results and a derived bound -- scales at every k position, checkpoint magnitudes, every
+# split-K structure, strides -- in tests/test_w8a16_engines_gpu.py.
 # ------------------------------------------------------------------------------------- #
 @pytest.mark.parametrize("name", G.names("w8a16_"))
 def test_w8a16_golden(name):
