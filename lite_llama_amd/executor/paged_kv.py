@@ -80,6 +80,9 @@ class PagedKVPool:
         position opens one); writes ``token_table[req, seq_len - 1]`` and returns / fills ``cur_select_index``."""
         return self._extend(req_idx, seq_len, 0, 1, 1, token_table, out=out)
 
+    def reserve(self, n: int) -> None:
+        """Nothing is reserved ahead: every step's :meth:`append` pops a block when a position opens one."""
+
     @torch.no_grad()
     def extend_at(self, req_idx: torch.Tensor, ctx_lens: torch.Tensor, chunk_lens: torch.Tensor, grid_len: int,
                   token_table: torch.Tensor, out=None) -> torch.Tensor:

@@ -28,6 +28,8 @@ from collections.abc import Sequence
 import torch
 
 from .. import _lib as L
+from .kv_pool import KVPool
+from .metadata import AttentionMetadata
 
 # the reference's capture grid (cuda_graph.py:27-28)
 DEFAULT_BATCH_SIZES: tuple[int, ...] = (1, 2, 4, 8, 16, 32, 64, 128)
@@ -62,8 +64,6 @@ class StepGraphs:
 
     def __init__(self, model, *, kv_buffer, b_req_tokens_table, batch_sizes=DEFAULT_BATCH_SIZES,
                  seq_len_buckets=DEFAULT_SEQ_LEN_BUCKETS, device="cuda"):
-        from . import AttentionMetadata
-
         self.model = model
         self.kv_buffer = kv_buffer
         self.b_req_tokens_table = b_req_tokens_table
@@ -77,7 +77,6 @@ class StepGraphs:
         self.cur_select_index = torch.zeros(cap, dtype=torch.int32, device=device)
         self.b_seq_len = torch.zeros(cap, dtype=torch.long, device=device)
         self.b_req_idx = torch.zeros(cap, dtype=torch.long, device=device)
-        self._meta = AttentionMetadata
         self._graphs: dict[tuple[int, int], tuple] = {}
         self._epoch = getattr(model, "layout_epoch", 0)  # the weight layouts the cached graphs were captured over
 
@@ -97,9 +96,9 @@ class StepGraphs:
 
     # ------------------------------------------------------------------ capture ----- #
     def _info(self, bs: int, bucket: int):
-        return self._meta(kv_buffer=self.kv_buffer, cur_select_index=self.cur_select_index[:bs],
-                          b_req_tokens_table=self.b_req_tokens_table, b_start_loc=None,
-                          b_req_idx=self.b_req_idx[:bs], b_seq_len=self.b_seq_len[:bs], max_actual_seq_len=bucket)
+        return AttentionMetadata(kv_buffer=self.kv_buffer, cur_select_index=self.cur_select_index[:bs],
+                                 b_req_tokens_table=self.b_req_tokens_table, b_start_loc=None,
+                                 b_req_idx=self.b_req_idx[:bs], b_seq_len=self.b_seq_len[:bs], max_actual_seq_len=bucket)
 
     def capture(self, bs: int, bucket: int):
         """Warm up on a side stream (fenced both ways), then record on the current stream.  The
@@ -171,8 +170,6 @@ class SlotRunner:
     pool, the request->rows table, the attention metadata struct and the captured-step grid."""
 
     def __init__(self, model, max_request_num: int, max_seq_len: int, device="cuda", kv_dtype=torch.float16):
-        from . import AttentionMetadata, KVPool
-
         geo = model.geo
         self.model = model
         self.device = device

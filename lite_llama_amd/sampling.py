@@ -52,6 +52,13 @@ class TokenLogprobs:
     top_logprobs: torch.Tensor
     top_ids: torch.Tensor
 
+    @classmethod
+    def blank(cls, rows: int, t: int, k: int, device) -> "TokenLogprobs":
+        """Buffers for ``t`` tokens per row and ``k`` alternatives, at the values of "nothing reported": 0.0 / 0.0 / id -1."""
+        return cls(torch.zeros(rows, t, dtype=torch.float32, device=device),
+                   torch.zeros(rows, t, k, dtype=torch.float32, device=device),
+                   torch.full((rows, t, k), -1, dtype=torch.int64, device=device))
+
     def cumulative(self, lengths: torch.Tensor | None = None) -> torch.Tensor:
         """``[rows]``: the sum of ``chosen`` over the first ``lengths[i]`` columns of row ``i`` (all columns by default) --
         a sample's cumulative log-probability, a scored text's log-likelihood."""

@@ -132,6 +132,34 @@ def test_extend_at_never_maps_pads_to_prefix_rows(block_size):
     assert len(set(owned)) == len(owned)                        # every named row belongs to one position
 
 
+@pytest.mark.parametrize("ctx0", [0, 9])
+def test_bump_pool_extend_at_writes_the_cells_the_plan_lists(ctx0):
+    """KVPool.extend_at against the plan's own ``valid_rows / valid_cols / valid_flat``: rows come off the cursor in grid
+    order, the table cells of the valid positions name them, every other cell keeps its value."""
+    from lite_llama_amd.executor import KVPool
+
+    lens, width = [5, 17, 1, 12], 40 - ctx0
+    req = torch.arange(4, dtype=torch.int32)
+    table = torch.randint(1000, 2000, (6, 40), generator=torch.Generator().manual_seed(1), dtype=torch.int32)
+    want, pool, used = table.clone(), KVPool(1, 4000, 1, 8, "cpu"), 0
+    for plan in plan_prefill_chunks(lens, width, 6):
+        select = pool.extend_at(req, plan.b_ctx_len + ctx0, plan.b_q_len, plan.width, table)
+        rows = torch.arange(used, used + 4 * plan.width, dtype=torch.int32)
+        used += 4 * plan.width
+        want[plan.valid_rows, plan.valid_cols + ctx0] = rows[plan.valid_flat]
+        assert torch.equal(select, rows) and select.dtype == torch.int32 and pool.used == used
+        assert torch.equal(table, want), plan.col0
+    # the padded grid of a one-step prefill is the chunk at context 0
+    one = table.clone()
+    assert torch.equal(pool.admit(req, torch.tensor(lens, dtype=torch.int32), 17, one), torch.arange(used, used + 68, dtype=torch.int32))
+    for i, n in enumerate(lens):
+        assert one[i, :n].tolist() == list(range(used + 17 * i, used + 17 * i + n)) and torch.equal(one[i, n:], table[i, n:])
+    assert torch.equal(one[4:], table[4:])
+    # a grid wider than what is left of the table rows: the valid positions are named, nothing is indexed past the row
+    end = pool.extend_at(req[:2], torch.tensor([35, 38], dtype=torch.int32), torch.tensor([5, 2], dtype=torch.int32), 8, one)
+    assert one[0, 35:].tolist() == end[:5].tolist() and one[1, 38:].tolist() == end[8:10].tolist()
+
+
 class _Runner:
     """The slice of SlotRunner that SlotBatch reads, on the CPU."""
 
