@@ -721,6 +721,35 @@ int ll_constraint_advance(int32_t* states, const int64_t* chosen, const int32_t*
                           const int32_t* next_states, const int32_t* finished, int32_t* error, int64_t batch,
                           int num_states, void* stream);
 
+/* ---- greedy speculative decoding (csrc/speculative.hip; executor/speculative.py states the semantics) -----------------
+ * Per row (all int32 [batch] unless said otherwise): history [batch][history_stride] = prompt, prefill's token, emitted
+ * tokens; hist_len; emitted (returned tokens so far); finished; max_tokens (optional).  The step's grid: ids / positions
+ * int64 [batch][num_draft_tokens + 1], q_len, ctx_len.
+ * ll_spec_draft: one workgroup per row writes the grid row -- column 0 the row's last token, then a draft of at most
+ *   min(num_draft_tokens, remaining - 1, max_seq_len - hist_len - 1) tokens looked up by the row's last n tokens
+ *   (n = max_ngram down to min_ngram) in `predicted` (int32 [batch][predicted_stride], predicted_lens optional, nearest end
+ *   to `emitted`) and then, with use_ngram, in the history (latest end); q_len = 1 + draft, ctx_len = hist_len - 1; a
+ *   finished row gets q_len = 0.  Histories of up to LL_SPEC_LDS_TOKENS tokens are staged in LDS.
+ * ll_spec_accept: one workgroup; argmax int64 [batch * (num_draft_tokens + 1)] = the model's token after every grid cell.
+ *   A running row keeps argmax[0 .. a], a = its leading drafts equal to the argmax one cell earlier, cut after the first
+ *   token that is a stop id (reasons 1), reaches max_tokens (3) or max_new_tokens (0): appended to out (int64, column
+ *   1 + emitted) and the history; lengths, verify_steps, drafted, accepted, accepted_per_step [batch][per_step_stride]
+ *   (column step[0]) follow; running[0] = rows still running; step[0] += 1.  Finished rows are not touched. */
+#define LL_SPEC_MAX_DRAFT 15
+#define LL_SPEC_MAX_NGRAM 16
+#define LL_SPEC_LDS_TOKENS 4096
+int ll_spec_draft(const int32_t* history, int64_t history_stride, const int32_t* hist_len, const int32_t* emitted,
+                  const int32_t* finished, const int32_t* max_tokens, int max_new_tokens, int max_seq_len,
+                  int num_draft_tokens, int max_ngram, int min_ngram, int use_ngram, const int32_t* predicted,
+                  int64_t predicted_stride, int predicted_cols, const int32_t* predicted_lens, int64_t* ids,
+                  int64_t* positions, int32_t* q_len, int32_t* ctx_len, int64_t batch, void* stream);
+int ll_spec_accept(const int64_t* argmax, const int64_t* ids, const int32_t* q_len, int64_t* out, int64_t out_stride,
+                   int64_t out_cols, int32_t* history, int64_t history_stride, int history_cols, int32_t* hist_len,
+                   int32_t* emitted, int32_t* finished, int32_t* lengths, int32_t* reasons, const int32_t* max_tokens,
+                   int max_new_tokens, const int64_t* stop_ids, int n_stop_ids, int32_t* verify_steps, int32_t* drafted,
+                   int32_t* accepted, int32_t* accepted_per_step, int64_t per_step_stride, int per_step_cols,
+                   int32_t* step, int32_t* running, int64_t batch, int num_draft_tokens, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,8 @@ SIGNATURES = {
     "ll_constrained_argmax": [P, P, P, P, P, P, P, P, L, L, L, I, I, P],
     "ll_constraint_mask": [P, P, P, P, P, P, L, L, L, L, I, I, P],
     "ll_constraint_advance": [P, P, P, P, P, P, P, L, I, P],
+    "ll_spec_draft": [P, L, P, P, P, P, I, I, I, I, I, I, P, L, I, P, P, P, P, P, L, P],
+    "ll_spec_accept": [P, P, P, P, L, L, P, L, I, P, P, P, P, P, P, I, P, I, P, P, P, P, L, I, P, P, L, I, P],
 }
 
 _RETURNS_I64 = {"ll_kv_alloc_scratch_bytes", "ll_tp_oneshot_flag_words", "ll_moe_router_workspace_floats", "ll_moe_align_workspace_ints",

@@ -14,7 +14,11 @@ MI355X-first differences from the reference (extensions, not parity changes):
     per-row ``max_tokens`` -- the decision is taken on the device inside the captured step (csrc/decode_stop.hip in
     ``ll_decode_advance``'s place, executor/stopping.py), finished rows are frozen, the results say where and why each
     row ended (``last_lengths`` / ``last_finish_reasons``) and the loop ends early once every row has, without a host
-    synchronisation per step.  Without ``stop`` the loop is the reference's: lockstep, ``max_new_tokens`` steps.
+    synchronisation per step.  Without ``stop`` the loop is the reference's: lockstep, ``max_new_tokens`` steps;
+  * the reference emits one token per row per forward; ``decode(speculate=Speculation(...))`` verifies up to ``k`` drafted
+    tokens per row in one forward over a ``[B, k + 1]`` grid on the paged pool (drafts from the row's own n-grams and from a
+    caller's prediction, greedy acceptance, csrc/speculative.hip + executor/speculative.py): the tokens are those of the same
+    grid with empty drafts, a row advances by every accepted draft plus one.
 """
 
 from .. import _lib as L  # noqa: F401
@@ -29,5 +33,7 @@ from .kv_cache_manager import KVCacheManager  # noqa: F401
 from .kv_pool import KVPool  # noqa: F401
 from .metadata import AttentionMetadata  # noqa: F401
 from .slots import DEFAULT_BATCH_SIZES, DEFAULT_SEQ_LEN_BUCKETS, SlotBatch, SlotRunner, StepGraphs, slot_advance  # noqa: F401
+from .speculative import (LDS_HISTORY_TOKENS, MAX_DRAFT_TOKENS, MAX_NGRAM, SpecState, Speculation, SpeculationStats,  # noqa: F401
+                          spec_accept, spec_draft)
 from .stopping import (MAX_STOP_SEQUENCE_LEN, MAX_STOP_SEQUENCES, MAX_STOP_TOKEN_IDS, RunningWatch, StopCriteria,  # noqa: F401
                        StopState, redirect_finished, stop_advance)

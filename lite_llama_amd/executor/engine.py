@@ -15,6 +15,7 @@ from .constraints import ConstrainedRows, constrained_argmax, constraint_advance
 from .kv_pool import KVPool
 from .metadata import AttentionMetadata
 from .paged_kv import PagedKVPool
+from .speculative import SpecState, Speculation, SpeculationStats, spec_accept, spec_draft
 from .stopping import RunningWatch, StopCriteria, StopState, redirect_finished, stop_advance
 
 
@@ -97,6 +98,11 @@ class DecodeEngine:
         # ... and the device tensors _begin_decode makes for it (one that a step writes belongs in :meth:`_step_tensors` too)
         self._input_ids = self._out = self._step = self._row_base = None
         self._lp: TokenLogprobs | None = None
+        # speculative decoding (extension): the prompt grid and lengths the last plain prefill was given (references, no
+        # copy) or why there is none; the state of the running speculative decode; the statistics of the last one
+        self._prompt, self._no_prompt = None, "no prefill has run"
+        self._spec: SpecState | None = None
+        self.last_speculation: SpeculationStats | None = None
         if hasattr(model, "rotary_emb") and torch.device(device).type == "cuda":
             model.rotary_emb.ensure(max_seq_len + 1, device, model.embed_tokens.weight.dtype)
 
@@ -142,10 +148,14 @@ class DecodeEngine:
             constraint.reset()
             self._constraint = constraint
         if num_samples is not None:
+            self._no_prompt = "prefill(num_samples=...): the rows share KV blocks of one prompt"
             return self._prefill_samples(prompt_ids, prompt_lens, sampling, chunk_size, int(num_samples))
         if shared_prefix_ids is not None:
+            self._no_prompt = "prefill(shared_prefix_ids=...): the rows share the prefix's KV rows"
             return self._first_tokens(self._prefill_shared(shared_prefix_ids, prompt_ids, prompt_lens, chunk_size), sampling)
-        return self._first_tokens(self._prefill_grid(prompt_ids, prompt_lens, chunk_size), sampling)
+        last = self._prefill_grid(prompt_ids, prompt_lens, chunk_size)
+        self._prompt = (prompt_ids, self.info.b_seq_len)  # what a speculative decode seeds its token history from
+        return self._first_tokens(last, sampling)
 
     def _reset_prefill_extras(self) -> None:
         """What only some prefill routes set, back to "not set": called on entry by everything that fills the pool
@@ -154,6 +164,7 @@ class DecodeEngine:
         info.shared_prefix_len, info.shared_prefix_req = 0, 0
         info.b_ctx_len, info.max_ctx_len = None, 0
         self.first_logprobs = None
+        self._prompt, self._no_prompt = None, "the pool was last filled by score() or synthetic_context(), not by a prefill"
 
     def _requests(self, n: int, stride: int = 1) -> torch.Tensor:
         idx = torch.arange(n, dtype=torch.int32, device=self.device)
@@ -434,6 +445,8 @@ class DecodeEngine:
         a trace in.  The log-probability buffers (_lp) have no place here: the warm-up step and the capture write the very
         column (_step, which IS restored) that the first replay writes again, with the same values."""
         info = self.info
+        if self._spec is not None:  # a speculative decode: the verify step's state (SpecState lists it)
+            return list(self._spec.tensors()) + [info.b_req_tokens_table]
         tensors = [self._input_ids, self._positions, info.cur_select_index, info.b_seq_len, self._step, self._out,
                    info.b_req_tokens_table]
         for part in (self._stop, self._constraint):
@@ -450,7 +463,9 @@ class DecodeEngine:
         self.pool.restore(snap[1])
 
     def _step_body(self):
-        """forward -> greedy sample -> record -> advance metadata (all on device)."""
+        """forward -> greedy sample -> record -> advance metadata (all on device); the verify step of a speculative decode."""
+        if self._spec is not None:
+            return self._spec_step()
         logits = self.model(self._input_ids, self._positions, self.info)[:, -1, :]
         nxt = self._sample(logits)
         if self._lp is not None:
@@ -531,7 +546,7 @@ class DecodeEngine:
     def decode(self, first_tokens: torch.Tensor, max_new_tokens: int, use_graph: bool = True,
                warmup_steps: int = 0, on_step=None, sampling=None, steps_per_graph: int = 1,
                logprobs: int | None = None, stop: StopCriteria | None = None,
-               constraint: ConstrainedRows | None = None) -> torch.Tensor:
+               constraint: ConstrainedRows | None = None, speculate: Speculation | None = None) -> torch.Tensor:
         """Generate ``max_new_tokens`` greedy tokens per row; returns ``[B, max_new_tokens]``.
 
         With ``use_graph`` the step is captured once (``max_actual_seq_len`` baked as the final
@@ -564,8 +579,16 @@ class DecodeEngine:
         the step holds exactly the launches it holds without them: the draw then runs ``ll_sample_filtered`` in
         ``ll_sample_top_p``'s place (sampling.sample_filtered has the rule), here and in :meth:`prefill`; under a
         ``constraint`` the filters see the masked copy, so top-k counts among the allowed tokens.
+        ``speculate`` (extension, :class:`Speculation`; ``None``: every step holds exactly the launches it holds without
+        it): greedy speculative decoding on the paged pool, :meth:`_decode_speculative` -- every step verifies up to ``k``
+        drafted tokens per row in one forward over a ``[B, k + 1]`` grid and a row advances by every draft the model agrees
+        with plus one; ``self.last_speculation`` then holds the acceptance statistics.
         """
+        if speculate is not None:
+            return self._decode_speculative(first_tokens, max_new_tokens, speculate, use_graph, on_step, sampling,
+                                            steps_per_graph, logprobs, stop, constraint)
         self._set_decode_options(first_tokens, sampling, logprobs, stop, constraint)
+        self._prompt, self._no_prompt = None, "a decode has already continued the last prefill"
         self._begin_decode(first_tokens, max_new_tokens)
         watch = RunningWatch(self._stop) if stop is not None and stop.check_every > 0 else None
         info = self.info
@@ -589,6 +612,7 @@ class DecodeEngine:
             constraint.validate(self.model.geo.vocab_size, self._batch)
         self._logprobs_k = _check_logprobs(logprobs)
         self.last_logprobs = self.last_lengths = self.last_finish_reasons = self.last_steps_run = None
+        self.last_speculation = self._spec = None
         self._stop = None
         if stop is not None:
             stop.validate(self.model.geo.vocab_size, self._batch)
@@ -666,6 +690,101 @@ class DecodeEngine:
         if self._lp is not None:
             self.last_logprobs = TokenLogprobs(self._lp.chosen[:, 1:], self._lp.top_logprobs[:, 1:], self._lp.top_ids[:, 1:])
         return self._out[:, 1:]
+
+    # ------------------------------------------------------ speculative decode ------ #
+    def _decode_speculative(self, first_tokens, max_new_tokens: int, spec: Speculation, use_graph: bool, on_step, sampling,
+                            steps_per_graph: int, logprobs, stop: StopCriteria | None, constraint) -> torch.Tensor:
+        """``decode(speculate=...)``: at most ``max_new_tokens`` verify steps, each ONE forward over a ``[B, k + 1]`` grid
+        (executor/speculative.py has the rules).  The step is the draft launch, the pool's ``extend_at``, the model's chunk
+        step (the attention of a chunked prefill, the decode GEMMs while ``B (k + 1) <= 64``), the argmax over all
+        ``B (k + 1)`` logits rows and the accept launch; nothing in it reads a length from the host, so with ``use_graph``
+        it is captured once and replayed.  The loop ends early once no row is running (rows also finish at
+        ``max_new_tokens``): every ``check_every`` steps, one interval late, as with ``stop``.  ``self.last_speculation``
+        holds the statistics, ``self.last_steps_run`` the steps issued; with ``stop`` (stop ids, ``max_tokens``, the pad)
+        ``last_lengths`` / ``last_finish_reasons`` are filled and the columns at and beyond a row's length read as the pad.
+        Call :meth:`prefill` again before the next decode."""
+        self.last_logprobs = self.last_lengths = self.last_finish_reasons = self.last_steps_run = None
+        self.last_speculation = None
+        self._stop = self._constraint = self._sampling = self._logprobs_k = None
+        if not isinstance(spec, Speculation):
+            raise ValueError("speculate must be a Speculation")
+        if not self.paged:
+            raise ValueError("speculative decoding needs the paged pool (kv_block_size): on the bump pool every verify step "
+                             "would burn B * (k + 1) fresh rows")
+        if self.pool.kv_buffer[0].element_size() == 1:
+            raise ValueError("speculative decoding is not served on an e4m3 KV pool")
+        for name, given in (("sampling", sampling), ("logprobs", logprobs), ("constraint", constraint)):
+            if given is not None:
+                raise ValueError(f"speculative decoding is greedy acceptance only: {name} cannot be combined with speculate")
+        if int(steps_per_graph) > 1:
+            raise ValueError("speculative decoding captures one verify step per graph: steps_per_graph must be 1")
+        if self._prompt is None:
+            raise ValueError(f"speculative decoding needs the prompt of a plain prefill on this engine: {self._no_prompt}")
+        b, info, k = self._batch, self.info, spec.num_draft_tokens
+        vocab = self.model.geo.vocab_size
+        if stop is not None:
+            if stop.stop_sequences:
+                raise ValueError("speculative decoding does not serve stop_sequences: a sequence may complete inside an "
+                                 "accepted run")
+            stop.validate(vocab, b)
+        spec.validate(vocab, b)
+        if first_tokens.numel() != b:
+            raise ValueError(f"first_tokens holds {first_tokens.numel()} tokens for a batch of {b}")
+        max_new_tokens = int(max_new_tokens)
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        width = int(info.max_actual_seq_len)                    # the prompt grid's width bounds every prompt length
+        if width + k + 1 > self.max_seq_len:
+            raise ValueError(f"a verify step of {k + 1} positions does not fit behind a prompt of {width} in max_seq_len "
+                             f"{self.max_seq_len}")
+        if width + max_new_tokens > self.max_seq_len:
+            raise RuntimeError(f"context {width + max_new_tokens} exceeds max_seq_len {self.max_seq_len}")
+        prompt_ids, prompt_lens = self._prompt
+        self._prompt, self._no_prompt = None, "a speculative decode has already continued the last prefill"
+        st = self._spec = SpecState(spec, stop, prompt_ids, prompt_lens, first_tokens, max_new_tokens, self.max_seq_len,
+                                    self.device)
+        # the chunk step's metadata: every length is a device tensor the draft launch rewrites, the grid is static
+        info.b_seq_len, info.b_ctx_len, info.b_start_loc = st.q_len, st.ctx_len, st.b_start_loc
+        info.cur_select_index = st.cur_select_index
+        info.max_actual_seq_len, info.max_ctx_len = k + 1, self.max_seq_len
+        try:
+            graph = None
+            if use_graph:
+                graph = self._capture(1, self._warm_up())      # _step_body / _step_tensors serve the verify step
+            watch = RunningWatch(st) if spec.check_every > 0 else None
+            steps_run = 0
+            while steps_run < max_new_tokens:
+                if on_step is not None:
+                    on_step(steps_run)
+                if graph is not None:
+                    graph.replay()
+                else:
+                    self._spec_step()
+                steps_run += 1
+                if watch is not None and watch.all_finished(steps_run):
+                    break
+        finally:
+            info.b_ctx_len, info.max_ctx_len = None, 0
+            self._spec = None
+        self._check_device_errors()
+        self.last_steps_run = steps_run
+        self.last_speculation = SpeculationStats(st.verify_steps, st.drafted, st.accepted,
+                                                 st.accepted_per_step[:, :steps_run], steps_run)
+        if stop is not None:
+            self.last_lengths, self.last_finish_reasons = st.lengths, st.reasons
+        return st.out[:, 1:]
+
+    def _spec_step(self) -> None:
+        """draft -> KV cells -> forward -> argmax -> accept (all on device)."""
+        st, info = self._spec, self.info
+        spec_draft(st)
+        # No rollback of rejected positions: a row's ctx only counts tokens it emitted, so the cells of a rejected draft lie
+        # at positions >= the new ctx.  The blocks behind them stay with the row (the pool never shrinks a request), this
+        # extend derives the same table cells from them again, and the step's K/V scatter overwrites them before the
+        # attention reads -- which, causal over ctx + j, never looks past the cells this very step wrote.
+        self.pool.extend_at(info.b_req_idx, st.ctx_len, st.q_len, st.k + 1, info.b_req_tokens_table, out=st.cur_select_index)
+        logits = self.model(st.ids, st.positions, info)
+        spec_accept(st, greedy_argmax(logits).view(-1))
 
     def _check_device_errors(self) -> None:
         """Sticky device-side error words, read where the host synchronises anyway (end of a decode): a lost peer of the
