@@ -680,6 +680,29 @@ int ll_sample_filtered(int64_t* out, const void* logits, const float* temperatur
                        const int32_t* top_k, const float* min_p, const float* uniform, const void* greedy,
                        int64_t batch, int64_t vocab, int64_t stride, int dtype, void* stream);
 
+/* ll_logit_penalties: repetition, presence and frequency penalties and a sparse per-row logit bias in one launch, one read of
+ * the logits and one write of out (csrc/sampler_penalties.hip).  Per row b and token v, with c = the number of entries j of
+ * the span with mask[b, j] != 0 and token_ids[b, j] == v (an id outside [0, vocab) is ignored), r / p / f the row's
+ * repetition / presence / frequency penalty (x_rows [batch] or NULL, then x_scalar) and bias the value the row's segment
+ * bias_ids / bias_values[bias_offsets[b] .. bias_offsets[b + 1]) names for v, in fp32 from the ORIGINAL stored logit z:
+ *   1. x = z + bias            (x = z where the row names none, or bias_offsets is NULL)
+ *   2. c > 0:  x = x < 0 ? x * r : x / r
+ *   3. x = fma(-f, c, x) - (c > 0 ? p : 0)
+ * and one rounding to out_dtype; the dtype pairs, strides, the mask and out != logits as ll_repetition_penalty.  With
+ * p = f = 0 and no bias the output is bit-equal to ll_repetition_penalty's.  span = 0 takes NULL token_ids / mask.  A row's
+ * segment names a token at most once, ids inside [0, vocab) (others are ignored); values finite or -inf.  batch <= 65535.
+ * No allocation, no host synchronisation, capturable.
+ * ll_seeded_uniform: out[b] (float) = (w >> 8) * 2^-24 with w the first output word of Philox4x32-10 at key
+ * (lo32, hi32 of seeds[b]) and counter (lo32, hi32 of *counter, 0, 0); counter NULL reads as 0.  In [0, 1), exact.  The
+ * counter is read on the device: a captured launch follows a step counter that the graph itself advances. */
+int ll_logit_penalties(void* out, const void* logits, const int64_t* token_ids, const void* mask,
+                       const float* repetition_rows, float repetition_scalar, const float* presence_rows,
+                       float presence_scalar, const float* frequency_rows, float frequency_scalar,
+                       const int32_t* bias_offsets, const int32_t* bias_ids, const float* bias_values, int64_t batch,
+                       int64_t vocab, int64_t span, int64_t logits_stride, int64_t out_stride, int64_t ids_stride,
+                       int64_t mask_stride, int in_dtype, int out_dtype, void* stream);
+int ll_seeded_uniform(float* out, const int64_t* seeds, const int64_t* counter, int64_t batch, void* stream);
+
 /* ---- token log-probabilities (the third kernel of the sampler row) -------------------------
  * Per row of logits [rows, vocab] (F16 / BF16 / F32, row stride in elements, unit column stride), with
  * lse = max + ln(sum exp(z - max)) accumulated in fp32 and col = *column (0 when column is NULL):

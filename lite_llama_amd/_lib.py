@@ -125,6 +125,8 @@ SIGNATURES = {
     "ll_repetition_penalty": [P, P, P, P, P, F, L, L, L, L, L, L, L, I, I, P],
     "ll_sample_top_p": [P, P, P, P, P, P, L, L, L, I, P],
     "ll_sample_filtered": [P, P, P, P, P, P, P, P, L, L, L, I, P],
+    "ll_logit_penalties": [P, P, P, P, P, F, P, F, P, F, P, P, P, L, L, L, L, L, L, L, I, I, P],
+    "ll_seeded_uniform": [P, P, P, L, P],
     "ll_argmax_split": [P, P, L, L, L, I, P, I, P],
     "ll_token_logprobs_scratch_bytes": [L, L, I],
     "ll_token_logprobs": [P, P, P, P, P, P, L, L, L, I, L, L, L, L, I, P, L, P],

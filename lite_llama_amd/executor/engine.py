@@ -8,8 +8,9 @@ from dataclasses import dataclass
 import torch
 
 from .. import _lib as L
-from ..sampling import (MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, apply_repetition_penalty, greedy_argmax,
-                        sample_with_filters, token_logprobs)
+from ..sampling import (MAX_TOP_LOGPROBS, Sampler, TokenLogprobs, _extras, _extras_off, _penalise, _penalty_off,
+                        apply_penalties, apply_repetition_penalty, greedy_argmax, resolve_sampling, sample_with_filters,
+                        seeded_uniform, token_logprobs)
 from .chunking import plan_prefill_chunks
 from .constraints import ConstrainedRows, constrained_argmax, constraint_advance, constraint_mask
 from .kv_pool import KVPool
@@ -91,6 +92,7 @@ class DecodeEngine:
         self.last_lengths = self.last_finish_reasons = self.last_steps_run = None
         # ---- the state of ONE decode: what the caller asked for, set by :meth:`decode` before :meth:`_begin_decode` ... ----
         self._sampling = None
+        self._seeds = None  # per-row seeds of the draw (``sampling.seed``); None: the draw is ``torch.rand``
         self._logprobs_k = None
         self._stop: StopState | None = None
         # constrained decoding (extension): the rows' automaton states of the running prefill / decode, when it has ``constraint``
@@ -234,14 +236,25 @@ class DecodeEngine:
     def _first_tokens(self, last: torch.Tensor, sampling) -> torch.Tensor:
         rows = self._constraint
         greedy = sampling is None or sampling.temperature == 0.0
+        # no token has been generated yet: of the penalties and the bias only ``sampling.logit_bias`` has something to act
+        # on -- the raw logits, before a constraint's mask, greedy or not; ``sampling.seed`` draws at counter 0
+        scored, seeds = last, None
+        if sampling is not None:
+            sampling, seeds = resolve_sampling(sampling, last.shape[0], last.shape[1], self.device)
+            bias = getattr(sampling, "logit_bias", None)
+            if bias is not None:
+                scored = apply_penalties(last, None, None, logit_bias=bias)
         if rows is not None and greedy:
-            tokens = constrained_argmax(last, rows)
+            tokens = constrained_argmax(scored, rows)
         elif greedy:
-            tokens = greedy_argmax(last)
+            tokens = greedy_argmax(scored)
         else:
-            uniform = torch.rand(last.shape[0], device=self.device)
-            drawn_from = last if rows is None else constraint_mask(last, rows)
-            tokens = Sampler().sample(drawn_from, sampling, None, uniform=uniform).view(-1)
+            uniform = torch.rand(last.shape[0], device=self.device) if seeds is None else seeded_uniform(seeds)
+            drawn_from = scored if rows is None else constraint_mask(scored, rows)
+            if scored is last:
+                tokens = Sampler().sample(drawn_from, sampling, None, uniform=uniform).view(-1)
+            else:  # the bias is in ``scored`` already
+                tokens = sample_with_filters(drawn_from, sampling, uniform).view(-1)
             if rows is not None:
                 constraint_advance(rows, tokens)
         if self._prefill_logprobs is not None:
@@ -476,7 +489,9 @@ class DecodeEngine:
     def _sample(self, logits: torch.Tensor) -> torch.Tensor:
         """Greedy argmax, or -- with ``sampling`` set by :meth:`decode` -- the reference sampler's sequence
         (repetition penalty over the tokens generated so far, then temperature + nucleus sampling) on
-        the HIP kernels; the uniform numbers come from ``torch.rand`` (graph-safe Philox)."""
+        the HIP kernels; the uniform numbers come from ``torch.rand`` (graph-safe Philox) or, with ``sampling.seed``, from
+        the rows' own seeds at the counter ``_step``.  With ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` on,
+        ``apply_penalties`` takes the repetition penalty's place (same span, same single pass over the logits)."""
         sp = self._sampling
         rows = self._constraint
         # rows that were finished when the step began keep their automaton state
@@ -485,21 +500,27 @@ class DecodeEngine:
             return greedy_argmax(logits) if rows is None else constrained_argmax(logits, rows, finished)
         b = self._batch
         generated = None
-        if sp.repetition_penalty != 1.0:
+        extras = _extras(sp)
+        extras_on = not _extras_off(*extras)
+        if sp.repetition_penalty != 1.0 or not (_penalty_off(extras[0]) and _penalty_off(extras[1])):
             span = self._out.shape[1]
             mask = torch.arange(span, device=self.device).unsqueeze(0) < self._step  # [1, span] -> rows share it
             generated = _Span(self._out, mask.expand(b, span))
-        uniform = torch.rand(b, device=self.device) if sp.temperature != 0.0 else None
+        uniform = None
+        if sp.temperature != 0.0:
+            uniform = torch.rand(b, device=self.device) if self._seeds is None else seeded_uniform(self._seeds, self._step)
         if rows is None:
             return Sampler().sample(logits, sp, generated, uniform=uniform).view(-1)
         # constrained: the penalty acts on the raw logits as it does above; greedy rows pick among the allowed tokens of
         # the (penalised) logits in one launch, sampled ones draw from a copy with the disallowed tokens at -inf
-        if generated is not None:
+        if extras_on:
+            logits = _penalise(logits, sp, generated, *extras)
+        elif generated is not None:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, sp.repetition_penalty)
         if sp.temperature == 0.0:
             return constrained_argmax(logits, rows, finished)
         # top_k / min_p of sp act on the masked copy: top-k counts among the allowed tokens
-        nxt = sample_with_filters(constraint_mask(logits, rows), sp, uniform).view(-1)
+        nxt = sample_with_filters(constraint_mask(logits, rows), sp, uniform).view(-1)  # (not Sampler: no second bias)
         constraint_advance(rows, nxt, finished)
         return nxt
 
@@ -579,6 +600,15 @@ class DecodeEngine:
         the step holds exactly the launches it holds without them: the draw then runs ``ll_sample_filtered`` in
         ``ll_sample_top_p``'s place (sampling.sample_filtered has the rule), here and in :meth:`prefill`; under a
         ``constraint`` the filters see the masked copy, so top-k counts among the allowed tokens.
+        ``sampling`` may also carry ``presence_penalty`` / ``frequency_penalty`` (floats), ``logit_bias`` (a ``{token: bias}``
+        dict for every row or a list with one dict / ``None`` per row; ``-inf`` bans a token) and ``seed`` (``None``, an int
+        ``s`` -- row ``i`` draws from seed ``s + i`` -- or one int per row) -- extension; absent or neutral, the step holds
+        exactly the launches it holds without them.  The penalties count the tokens of the span the repetition penalty
+        looks at and run with it in ``ll_logit_penalties`` (sampling.apply_penalties has the rule), on the raw logits
+        before a ``constraint``'s mask; :meth:`prefill` applies the bias to its token too.  With a seed the step that
+        writes column ``c`` of the output (the prefill's token is column 0) draws row ``i``'s number from the row's seed
+        and ``c`` alone (sampling.seeded_uniform): eager, captured and ``steps_per_graph`` runs draw the same numbers, and
+        a row's stream does not depend on the rows beside it.
         ``speculate`` (extension, :class:`Speculation`; ``None``: every step holds exactly the launches it holds without
         it): greedy speculative decoding on the paged pool, :meth:`_decode_speculative` -- every step verifies up to ``k``
         drafted tokens per row in one forward over a ``[B, k + 1]`` grid and a row advances by every draft the model agrees
@@ -618,7 +648,9 @@ class DecodeEngine:
             stop.validate(self.model.geo.vocab_size, self._batch)
             self._stop = StopState(stop, first_tokens, self.device)
         self._constraint = constraint
-        self._sampling = sampling  # None = greedy; else an object with temperature / top_p / repetition_penalty [/ top_k / min_p]
+        # None = greedy; else an object with temperature / top_p / repetition_penalty [/ top_k / min_p / presence_penalty /
+        # frequency_penalty / logit_bias / seed]: the bias is built into its device form and the seeds are laid out here, once
+        self._sampling, self._seeds = resolve_sampling(sampling, self._batch, self.model.geo.vocab_size, self.device)
 
     def _warm_up(self):
         """One eager step on a side stream (workspace growth, library init), fenced both ways (cuda_graph.py:110-115);

@@ -165,6 +165,197 @@ def apply_repetition_penalty(logits: torch.Tensor, token_ids: torch.Tensor, mask
     return out
 
 
+class LogitBias:
+    """A sparse additive bias on the logits, per row, as the device CSR ``ll_logit_penalties`` reads: ``offsets`` int32
+    ``[batch + 1]``, ``ids`` int32 and ``values`` fp32 ``[offsets[-1]]``.  Built once per call from ``bias``: one
+    ``{token: bias}`` dict for every row, or a list of ``batch`` dicts / ``None``s (``None``: that row has no bias).
+    Validated on the host: ids inside ``[0, vocab)``, values finite or ``-inf`` (a ban; ``+inf`` and NaN are refused)."""
+
+    def __init__(self, bias, batch: int, vocab: int, device):
+        per_row = [bias] * batch if bias is None or isinstance(bias, dict) else list(bias)
+        if len(per_row) != batch:
+            raise ValueError(f"logit_bias names {len(per_row)} rows for a batch of {batch}")
+        offsets, ids, values = [0], [], []
+        checked = set()  # a dict that serves every row is checked once
+        for row in per_row:
+            if row is not None and not isinstance(row, dict):
+                raise ValueError("logit_bias must be a {token: bias} dict, or a list of such dicts and Nones")
+            if row and id(row) not in checked:
+                checked.add(id(row))
+                for tok, val in row.items():
+                    if isinstance(tok, bool) or not isinstance(tok, int) or not 0 <= tok < vocab:
+                        raise ValueError(f"logit_bias names token {tok!r} outside the vocabulary of {vocab}")
+                    val = float(val)
+                    if val != val or val == float("inf"):
+                        raise ValueError(f"logit_bias of token {tok} is {val}: it must be finite or -inf")
+            if row:
+                ids.extend(int(t) for t in row)
+                values.extend(float(v) for v in row.values())
+            offsets.append(len(ids))
+        self.batch, self.vocab = batch, vocab
+        self.offsets = torch.tensor(offsets, dtype=torch.int32, device=device)
+        # never empty: the kernel is handed valid pointers even when no row names a token
+        self.ids = torch.tensor(ids or [0], dtype=torch.int32, device=device)
+        self.values = torch.tensor(values or [0.0], dtype=torch.float32, device=device)
+
+    @classmethod
+    def of(cls, bias, batch: int, vocab: int, device) -> "LogitBias | None":
+        """``bias`` as a :class:`LogitBias` for ``[batch, vocab]`` logits: ``None`` stays ``None``, one already built is
+        checked against the shape, a dict or a list is built."""
+        if bias is None:
+            return None
+        if isinstance(bias, cls):
+            if bias.batch != batch or bias.vocab != vocab:
+                raise ValueError(f"the LogitBias was built for {bias.batch} x {bias.vocab} logits, not {batch} x {vocab}")
+            return bias
+        return cls(bias, batch, vocab, device)
+
+
+def apply_penalties(logits: torch.Tensor, token_ids: torch.Tensor | None, mask: torch.Tensor | None,
+                    repetition_penalty=1.0, presence_penalty=0.0, frequency_penalty=0.0, logit_bias=None) -> torch.Tensor:
+    """New ``[batch, vocab]`` logits after the repetition, presence and frequency penalties over the generated span
+    ``token_ids`` / ``mask`` ``[batch, span]`` and the additive ``logit_bias`` (a :class:`LogitBias`, a dict or a list of
+    dicts), in one launch and one read of the logits (csrc/sampler_penalties.hip).  With ``c[v]`` the number of masked-in
+    span entries equal to ``v``, every token's value is computed in fp32 from the stored logit ``z[v]``:
+    ``x = z[v] + bias[v]``; if ``c[v] > 0``: ``x = x * r if x < 0 else x / r``; ``x = x - f * c[v] - (p if c[v] > 0 else 0)``.
+    Each penalty is a Python scalar or a ``[batch]`` / ``[batch, 1]`` tensor; the result dtype is that of
+    :func:`apply_repetition_penalty`: scalars keep the logits dtype, any tensor penalty promotes.  ``token_ids`` / ``mask``
+    may be ``None`` when only a bias is given.  With ``p = f = 0`` and no bias the result is bit-equal to
+    :func:`apply_repetition_penalty`'s, which stays the route for repetition-only calls."""
+    L.require_cuda(logits, token_ids, mask)
+    if logits.dim() != 2:
+        raise ValueError("logits must be [batch, vocab]")
+    batch, vocab = logits.shape
+    if (token_ids is None) != (mask is None):
+        raise ValueError("token_ids and mask come together")
+    if token_ids is not None and (token_ids.shape != mask.shape or token_ids.dim() != 2 or token_ids.shape[0] != batch):
+        raise ValueError("logits [batch, vocab], token_ids / mask [batch, span]")
+    if not torch.is_tensor(repetition_penalty) and not float(repetition_penalty) > 0.0:
+        raise ValueError(f"repetition_penalty must be positive, got {repetition_penalty}")
+    if logits.stride(1) != 1:
+        logits = logits.contiguous()
+    bias = LogitBias.of(logit_bias, batch, vocab, logits.device)
+    ids = msk = None
+    span = 0
+    if token_ids is not None and token_ids.shape[1] > 0:
+        ids = token_ids.to(torch.int64).contiguous()
+        msk = mask.to(torch.bool).contiguous()
+        span = ids.shape[1]
+    out_dtype = logits.dtype
+    rows, scalars = [], []
+    for pen, neutral in ((repetition_penalty, 1.0), (presence_penalty, 0.0), (frequency_penalty, 0.0)):
+        if torch.is_tensor(pen):
+            L.require_cuda(pen)
+            t = pen.reshape(-1).to(torch.float32).contiguous()
+            if t.numel() != batch:
+                raise ValueError("a tensor penalty needs one entry per row")
+            out_dtype = torch.promote_types(out_dtype, pen.dtype)
+            rows.append(t)
+            scalars.append(neutral)
+        else:
+            rows.append(None)
+            scalars.append(float(pen))
+    out = torch.empty((batch, vocab), dtype=out_dtype, device=logits.device)
+    L.check(
+        L.lib().ll_logit_penalties(
+            out.data_ptr(), logits.data_ptr(), L.ptr(ids), L.ptr(msk), L.ptr(rows[0]), scalars[0], L.ptr(rows[1]),
+            scalars[1], L.ptr(rows[2]), scalars[2], L.ptr(bias.offsets if bias else None),
+            L.ptr(bias.ids if bias else None), L.ptr(bias.values if bias else None), batch, vocab, span,
+            logits.stride(0), out.stride(0), ids.stride(0) if span else 0, msk.stride(0) if span else 0,
+            L.dtype_code(logits.dtype), L.dtype_code(out_dtype), L.stream_ptr()),
+        "apply_penalties")
+    return out
+
+
+def seeded_uniform(seeds: torch.Tensor, column: torch.Tensor | None = None) -> torch.Tensor:
+    """``seeds [batch]`` (int64) -> fp32 ``[batch]`` in ``[0, 1)``: row ``b``'s number is the top 24 bits of the first
+    Philox4x32-10 word at key ``seeds[b]`` and counter ``column`` (a one-element int64 device tensor, read on the device
+    so a captured launch follows a counter the graph advances; ``None``: 0).  A row's numbers depend on its seed and the
+    counter alone -- not on the batch it sits in, nor on what else has drawn random numbers."""
+    L.require_cuda(seeds, column)
+    if seeds.dtype != torch.int64 or seeds.dim() != 1:
+        raise ValueError("seeds must be an int64 [batch] tensor")
+    if column is not None and (column.dtype != torch.int64 or column.numel() != 1):
+        raise ValueError("column must be a one-element int64 tensor")
+    seeds = seeds.contiguous()
+    out = torch.empty(seeds.numel(), dtype=torch.float32, device=seeds.device)
+    L.check(L.lib().ll_seeded_uniform(out.data_ptr(), seeds.data_ptr(), L.ptr(column), seeds.numel(), L.stream_ptr()),
+            "seeded_uniform")
+    return out
+
+
+def row_seeds(seed, batch: int, device) -> torch.Tensor | None:
+    """``SamplingParams.seed`` as the int64 ``[batch]`` seeds of :func:`seeded_uniform`: ``None`` stays ``None``, an int
+    ``s`` gives row ``i`` the seed ``s + i`` (wrapping to int64), a sequence gives one seed per row."""
+    if seed is None:
+        return None
+    if isinstance(seed, int):
+        values = [seed + i for i in range(batch)]
+    else:
+        values = [int(s) for s in (seed.tolist() if torch.is_tensor(seed) else seed)]
+        if len(values) != batch:
+            raise ValueError(f"seed names {len(values)} rows for a batch of {batch}")
+    return torch.tensor([(v + 2 ** 63) % 2 ** 64 - 2 ** 63 for v in values], dtype=torch.int64, device=device)
+
+
+@dataclass
+class SamplingParams:
+    """The sampling options :class:`Sampler` and ``DecodeEngine`` read, in one place (any object with ``temperature``,
+    ``top_p`` and ``repetition_penalty`` keeps being accepted).  ``logit_bias``: see :class:`LogitBias`; ``seed``: see
+    :func:`row_seeds` -- read by the engine, which owns the draw."""
+
+    temperature: float = 1.0
+    top_p: float = 1.0
+    repetition_penalty: float = 1.0
+    top_k: int = 0
+    min_p: float = 0.0
+    presence_penalty: float = 0.0
+    frequency_penalty: float = 0.0
+    logit_bias: object = None
+    seed: object = None
+
+
+def _penalty_off(value) -> bool:
+    return value is None or (not torch.is_tensor(value) and float(value) == 0.0)
+
+
+def _extras_off(presence, frequency, bias) -> bool:
+    """Presence penalty, frequency penalty and bias off for every row, decided on the host without reading a tensor."""
+    return bias is None and _penalty_off(presence) and _penalty_off(frequency)
+
+
+def _extras(params):
+    return (getattr(params, "presence_penalty", 0.0), getattr(params, "frequency_penalty", 0.0),
+            getattr(params, "logit_bias", None))
+
+
+def resolve_sampling(params, batch: int, vocab: int, device):
+    """What an engine does once per call with the caller's parameter object -> ``(params, seeds)``: ``seeds`` are
+    :func:`row_seeds` of ``params.seed`` (``None`` without one), and a ``logit_bias`` given as a dict or a list is built
+    into its :class:`LogitBias` on a copy of the parameters, so that no step builds it again (a step may be captured).
+    An object without ``logit_bias`` and ``seed`` comes back as it is, and nothing is put on the device."""
+    if params is None:
+        return None, None
+    seeds = row_seeds(getattr(params, "seed", None), batch, device)
+    presence, frequency, bias = _extras(params)
+    if bias is None:
+        return params, seeds
+    built = LogitBias.of(bias, batch, vocab, device)
+    if built is bias:
+        return params, seeds
+    return SamplingParams(params.temperature, params.top_p, params.repetition_penalty, getattr(params, "top_k", 0),
+                          getattr(params, "min_p", 0.0), presence, frequency, built, getattr(params, "seed", None)), seeds
+
+
+def _penalise(logits, params, generated, presence, frequency, bias) -> torch.Tensor:
+    """:func:`apply_penalties` in :func:`apply_repetition_penalty`'s place; with a bias also without a generated span."""
+    if generated is None and bias is None:
+        return logits
+    ids, mask = (None, None) if generated is None else (generated.token_ids, generated.mask)
+    return apply_penalties(logits, ids, mask, params.repetition_penalty, 0.0 if presence is None else presence,
+                           0.0 if frequency is None else frequency, bias)
+
+
 def sample_top_p(logits: torch.Tensor, temperature, top_p, uniform: torch.Tensor | None = None,
                  greedy: torch.Tensor | None = None) -> torch.Tensor:
     """Temperature + nucleus sampling of ``[batch, vocab]`` logits -> int64 ``[batch, 1]`` ids, the
@@ -262,14 +453,19 @@ class Sampler:
     """``Sampler.sample`` / ``sample_batched`` of the reference (sampler.py:199-270) on the kernels above.
     ``params``: any object with ``temperature``, ``top_p``, ``repetition_penalty`` (scalars for
     ``sample``; ``[batch, 1]`` tensors plus ``greedy`` / ``all_greedy`` / ``any_penalty`` for
-    ``sample_batched``) and, optionally, ``top_k`` / ``min_p`` (extension, default off: scalars or per-row tensors);
+    ``sample_batched``) and, optionally, ``top_k`` / ``min_p`` (extension, default off: scalars or per-row tensors) and
+    ``presence_penalty`` / ``frequency_penalty`` / ``logit_bias`` (extension, default off: with any of them on,
+    :func:`apply_penalties` takes :func:`apply_repetition_penalty`'s place, and a bias acts without ``generated`` too);
     ``generated``: object with ``token_ids`` and ``mask``."""
 
     @torch.no_grad()
     def sample(self, logits, params, generated=None, uniform=None):
         if logits.dim() == 3:
             logits = logits[:, -1, :]
-        if params.repetition_penalty != 1.0 and generated is not None:
+        extras = _extras(params)
+        if not _extras_off(*extras):
+            logits = _penalise(logits, params, generated, *extras)
+        elif params.repetition_penalty != 1.0 and generated is not None:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, params.repetition_penalty)
         if params.temperature == 0.0:
             return greedy_argmax(logits).view(-1, 1)
@@ -279,7 +475,10 @@ class Sampler:
     def sample_batched(self, logits, params, generated=None, uniform=None):
         if logits.dim() == 3:
             logits = logits[:, -1, :]
-        if params.any_penalty and generated is not None:
+        extras = _extras(params)
+        if not _extras_off(*extras):
+            logits = _penalise(logits, params, generated, *extras)
+        elif params.any_penalty and generated is not None:
             logits = apply_repetition_penalty(logits, generated.token_ids, generated.mask, params.repetition_penalty)
         if params.all_greedy:
             return greedy_argmax(logits).view(-1, 1)
